@@ -25,8 +25,8 @@ Multi-GPU (one process per GPU, torch.distributed over RCCL; --route):
              every target; alltoall: all_to_all_single by target slice, each rank merges its
              q / N targets), K3 merge.  value = the 65,536 targets / the slowest rank's step.
              Consecutive steps rotate over --inflight streams, so one step's exchange overlaps
-             the next step's K6.  The other exchange and the prefix route are measured beside
-             it (extra: broadcast_<exchange>, prefix_strong -- the same problem on the prefix
+             the next step's K6.  With --full the other exchange and the prefix route are measured
+             beside it (extra: broadcast_<exchange>, prefix_strong -- the same problem on the prefix
              route -- and prefix_weak), each labelled.
   prefix     ids AND targets are partitioned by their top log2(N) bits; each rank answers only
              its own targets from its own shard.  If every shard holds >= k ids, a target's
@@ -37,7 +37,11 @@ totals) or "weak" (default with the prefix route: every rank keeps the one-GPU w
 --n ids and --q targets per GPU out of a global problem N times as large; value = all ranks'
 targets / the slowest rank's time).  N = 1 runs the one-GPU K6 over the whole set.
 
-Beside the headline (`value`) the line carries, measured in the same run:
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit,
+ms_per_step, the configuration); --dump-outputs DIR also writes the last timed step's results
+(DIR/indices.npy, DIR/counts.npy; the inputs are a function of the arguments alone, so two builds
+can be compared output for output).  With --full the line also carries, measured in the same run
+after the timed steps:
   roofline        F2 (the dominant K6 kernel) timed by events its own dispatches record over
                   serial calls after the timed steps; roofline_hbm: the same kernel with the Infinity Cache
                   evicted before each call (the cfg-2 working set otherwise stays in L3)
@@ -101,14 +105,24 @@ def parse(argv=None):
     ap.add_argument("--simulate-world", type=int, default=0,
                     help="prefix route only: run rank --simulate-rank of a world of this size on one GPU")
     ap.add_argument("--simulate-rank", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline: single-batch latency, "
+                         "per-kernel and roofline figures, the K1 scan, the small-batch / table / cfg 3-5 legs "
+                         "(N > 1: the other exchange, the prefix route, cfg 3), the oracle check and the CPU "
+                         "baselines.  Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the top-k node indices and the per-target "
+                         "counts) as DIR/<name>.npy in float64, after the timed steps")
     ap.add_argument("--cpu-targets", type=int, default=256, help="cpu_baseline sample (targets, all host threads)")
     ap.add_argument("--cpu-threads", type=int, default=os.cpu_count() or 1,
                     help="cpu_baseline threads (default: every host CPU, nproc; the rate at the job's cgroup CPU "
                          "quota and the single-core figures are reported too)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra legs (small batch, cfg 1/3/4/5)")
-    ap.add_argument("--no-scan", action="store_true", help="skip the reference K1 scan measurement")
-    ap.add_argument("--verify", type=int, default=16, help="targets re-checked against the oracle (rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the oracle check and the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="--full: skip the extra legs (small batch, cfg 1/3/4/5)")
+    ap.add_argument("--no-scan", action="store_true", help="--full: skip the reference K1 scan measurement")
+    ap.add_argument("--verify", type=int, default=16,
+                    help="--full: targets re-checked against the oracle (rank 0)")
     ap.add_argument("--inflight", type=int, default=3,
                     help="batch algo: consecutive steps rotate over this many streams, so one step's "
                          "latency-bound F3/F4 overlaps the other steps' HBM-bound F2 (1 = strictly serial; "
@@ -400,6 +414,25 @@ def l3_evict(buf):
     return buf.sum()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, idx, cnt, rank=None, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what the last timed step returned on this rank -- the (q, k) node indices
+    and the (q,) counts -- as float64 .npy files (a uint32 is exact there).  Past 64 MB in all, a
+    fixed seeded sample of the rows, with the sampled row numbers beside it."""
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if rank is None else f"_rank{rank}"
+    q, k = idx.shape
+    rows_max = max_bytes // (8 * (k + 2))
+    if q > rows_max:
+        rows = np.sort(np.random.default_rng(0).choice(q, size=rows_max, replace=False))
+        idx, cnt = idx[rows], cnt[rows]
+        np.save(os.path.join(d, f"rows{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, f"indices{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, f"counts{sfx}.npy"), cnt.astype(np.float64))
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -573,6 +606,54 @@ def main():
     got_idx = outs[last][0][:q_out].cpu().numpy().view(np.uint32).copy()
     got_tg = tgidx[:q_local].cpu().numpy().view(np.uint32).copy() if tgidx is not None \
         else np.arange(tlo, tlo + q_out)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, got_idx.reshape(-1, a.k),
+                     outs[last][1][:q_out].cpu().numpy().view(np.uint32), rank if world > 1 else None)
+
+    def headline():
+        par = {"prefix": f"prefix-routed shards x{G} (top {pbits} id bits; no data-path collective)",
+               "broadcast": f"id-range shards x{world}" + ((" + RCCL all-to-all by target slice + K3 merge" if a2a else
+                                                             " + RCCL all-gather + K3 merge") if collective else "")}[route]
+        return {
+            "metric": METRIC,
+            "value": (a.q_total if not a.simulate_world else q_local) / (ms_per_step * 1e-3),
+            "unit": "queries/s",
+            "n_gpus": world,
+            "dist_world_size": dist.get_world_size() if use_dist else 1,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": ms_per_step,
+            "host_enqueue_ms_per_step": t_enq * 1e3 / a.steps,   # rank 0's host time to enqueue a step
+            "gpu_window_ms_per_step": w_beg.elapsed_time(w_end) / a.steps,   # rank 0, GPU clock (diagnostic)
+            "higher_is_better": True,
+            "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "u32",
+            "data": "synthetic: splitmix64 ids and targets generated in HBM (SURVEY 8(d) spec)",
+            "config": {"workload": ("cfg2" if (a.n, a.q) == (1 << 24, 65536) else "custom")
+                                   + f" batched k-NN: {a.q} targets x {a.n} ids (2^{a.n.bit_length()-1}), k={a.k}"
+                                   + (f" per GPU ({a.q_total} x {a.n_total} over {G_eff} GPUs)"
+                                      if scaling == "weak" and G_eff > 1 else ""),
+                       "n_ids": a.n_total, "n_targets": a.q_total, "k": a.k, "algo": a.algo, "route": route,
+                       "ids_per_gpu": n_local, "targets_per_gpu": q_local, "parallelism": par,
+                       "inflight": D, "exchange": plan["exchange"],
+                       "results_on_this_rank": f"targets [{tlo}, {tlo + q_out})" if collective else None,
+                       "result_indices": ("shard-local" if a.shard_index == "local" else "global")
+                       if route == "prefix" and pbits else "global"},
+        }
+
+    if not a.full:   # the plain run: the headline alone (everything below is behind --full)
+        progress(f"timed {a.steps} steps: {ms_per_step:.4f} ms/step")
+        if rank == 0:
+            res = headline()
+            if a.simulate_world:
+                res["simulated"] = f"rank {R} of {G} on one GPU; value = this rank's targets / its step time"
+            os.write(_RESULT_FD, (json.dumps(res) + "\n").encode())
+        ctx.close()
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     progress(f"timed {a.steps} steps: {ms_per_step:.4f} ms/step; diagnostics")
     reps = max(3, min(a.steps, 20))
     res = {}
@@ -748,39 +829,7 @@ def main():
             extra["cfg3"] = {"error": repr(e)}
 
     if rank == 0:
-        par = {"prefix": f"prefix-routed shards x{G} (top {pbits} id bits; no data-path collective)",
-               "broadcast": f"id-range shards x{world}" + ((" + RCCL all-to-all by target slice + K3 merge" if a2a else
-                                                             " + RCCL all-gather + K3 merge") if collective else "")}[route]
-        res = {
-            "metric": METRIC,
-            "value": (a.q_total if not a.simulate_world else q_local) / (ms_per_step * 1e-3),
-            "unit": "queries/s",
-            "n_gpus": world,
-            "dist_world_size": dist.get_world_size() if use_dist else 1,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": ms_per_step,
-            "host_enqueue_ms_per_step": t_enq * 1e3 / a.steps,   # rank 0's host time to enqueue a step
-            "gpu_window_ms_per_step": w_beg.elapsed_time(w_end) / a.steps,   # rank 0, GPU clock (diagnostic)
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic: splitmix64 ids and targets generated in HBM (SURVEY 8(d) spec)",
-            "config": {"workload": ("cfg2" if (a.n, a.q) == (1 << 24, 65536) else "custom")
-                                   + f" batched k-NN: {a.q} targets x {a.n} ids (2^{a.n.bit_length()-1}), k={a.k}"
-                                   + (f" per GPU ({a.q_total} x {a.n_total} over {G_eff} GPUs)"
-                                      if scaling == "weak" and G_eff > 1 else ""),
-                       "n_ids": a.n_total, "n_targets": a.q_total, "k": a.k, "algo": a.algo, "route": route,
-                       "ids_per_gpu": n_local, "targets_per_gpu": q_local, "parallelism": par,
-                       "inflight": D, "exchange": plan["exchange"],
-                       "results_on_this_rank": f"targets [{tlo}, {tlo + q_out})" if collective else None,
-                       "result_indices": ("shard-local" if a.shard_index == "local" else "global")
-                       if route == "prefix" and pbits else "global"},
-            "latency_ms_per_batch": lat_ms,
-            "roofline": roof,
-            **res,
-        }
+        res = {**headline(), "latency_ms_per_batch": lat_ms, "roofline": roof, **res}
         if a.simulate_world:
             res["simulated"] = f"rank {R} of {G} on one GPU; value = this rank's targets / its step time"
         res.update(extra)

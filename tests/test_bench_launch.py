@@ -1,6 +1,7 @@
 """bench.py's multi-GPU launch (VERDICT r2 missing #1): `python bench.py --gpus N` started as one
 process runs N ranks under torch.distributed.run, decided before anything touches the GPU; and the
-bench's cfg-1/cfg-4 workload tables are the ones the reference's onNewNode grows.  CPU only."""
+bench's cfg-1/cfg-4 workload tables are the ones the reference's onNewNode grows.  CPU only, except
+the plain run with --dump-outputs (marked gpu)."""
 import json
 import os
 import subprocess
@@ -92,6 +93,53 @@ def test_bench_tables_are_onnewnode_grown():
             assert np.array_equal(g, w)
     myid, firsts, off, nodes = bench.cfg1_table(2024)
     assert 80 <= nodes.shape[0] <= 110 and off[-1] == nodes.shape[0]
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float64 .npy files, exact for uint32 values; past 64 MB in all a fixed
+    seeded row sample (the same rows on every run) with the row numbers beside it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--dump-outputs", str(tmp_path), "--steps", "3"])
+    assert a.dump_outputs == str(tmp_path) and a.steps == 3 and not a.full
+    assert bench.parse(["--full"]).full
+    idx = np.arange(40, dtype=np.uint32).reshape(5, 8) + np.uint32(0xFFFFFF00)
+    cnt = np.full(5, 8, np.uint32)
+    bench.dump_outputs(str(tmp_path / "a"), idx, cnt)
+    got = np.load(tmp_path / "a" / "indices.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, idx) and not (tmp_path / "a" / "rows.npy").exists()
+    assert np.array_equal(np.load(tmp_path / "a" / "counts.npy"), cnt)
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    limit = 1 << 16
+    rows_max = limit // (8 * 3)
+    big = np.arange(rows_max + 7, dtype=np.uint32).reshape(-1, 1)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, big[:, 0], rank=1, max_bytes=limit)
+    rows = np.load(tmp_path / "b" / "rows_rank1.npy")
+    assert rows.shape == (rows_max,) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "rows_rank1.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "indices_rank1.npy")[:, 0], rows)
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= limit + 3 * 128   # the arrays fit the limit; each .npy adds its 128-byte header
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run prints the headline alone (nothing of --full's legs) and --dump-outputs holds
+    what the timed path returned: bit-equal to the oracle over the same seeded inputs."""
+    n, q, k, seed = 100003, 301, 8, 77
+    (line,) = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--n", str(n), "--q", str(q), "--seed", str(seed),
+                    "--dump-outputs", str(tmp_path)])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert abs(line["value"] - q / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    for key in ("roofline", "latency_ms_per_batch", "cpu_baseline", "small_batch", "cfg3_shard", "verified_exact"):
+        assert key not in line
+    want, wcnt = O.topk(O.gen_ids(seed, n), O.gen_ids(seed + 1, q), k)
+    idx, cnt = np.load(tmp_path / "indices.npy"), np.load(tmp_path / "counts.npy")
+    assert idx.dtype == np.float64 and idx.shape == (q, k) and cnt.shape == (q,)
+    assert np.array_equal(idx, want) and np.array_equal(cnt, wcnt)
 
 
 def test_classify_threads_match():

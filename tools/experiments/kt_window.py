@@ -1,6 +1,6 @@
 """Per-kernel mean duration of the K6 calls [first, first + count) in a rocprofv3 kernel trace
 (each K6 kernel's dispatches in start order: dispatch j of k_f2_filter belongs to call j).
-bench.py --steps S --warmup W issues W warmup calls, S timed calls (two in flight), then
+bench.py --full --steps S --warmup W issues W warmup calls, S timed calls (two in flight), then
 max(3, min(S, 20)) serial calls timed by events (the roofline's kernels_ms): so
 `kt_window.py DIR W S` summarises the timed window and `kt_window.py DIR W+S R` the serial one.
 usage: kt_window.py DIR FIRST COUNT"""

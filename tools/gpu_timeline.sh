@@ -4,7 +4,7 @@
 set -o pipefail
 TAG=$1; shift; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 env "${@:-A=1}" rocprofv3 --kernel-trace --stats -d $OUT/kt -o run --output-format csv -- python3 bench.py --steps 400 --warmup 50 --no-cpu --no-extra --no-scan > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 300 env "${@:-A=1}" rocprofv3 --kernel-trace --stats -d $OUT/kt -o run --output-format csv -- python3 bench.py --full --steps 400 --warmup 50 --no-cpu --no-extra --no-scan > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python3 tools/experiments/kt_timeline.py $OUT/kt 300 6 > $OUT/timeline.txt 2>&1
 python3 tools/experiments/kt_overlap.py $OUT/kt > $OUT/overlap.txt 2>&1
 head -40 $OUT/timeline.txt; head -30 $OUT/overlap.txt

@@ -1,5 +1,5 @@
-"""One line per bench.py JSON result (the headline, its roofline, the cfg-3 legs): usage
-python tools/summarize_bench.py FILE..."""
+"""One line per bench.py JSON result (the headline and, from a `bench.py --full` run, its roofline
+and the cfg-3 legs): usage python tools/summarize_bench.py FILE..."""
 import json
 import sys
 
