@@ -105,6 +105,47 @@ int dhtgpu_set_sub_handles(dhtgpu_ctx* ctx, int on);
 int dhtgpu_sub_handles_active(dhtgpu_ctx* ctx, uint32_t q, uint32_t k);
 int dhtgpu_handles_to_indices_dev(dhtgpu_ctx* ctx, const uint32_t* handles, uint64_t m, uint32_t* out_idx,
                                   uint32_t idx_base, void* stream);
+/* Accept mask over the resident id set -- Node::isGood / isExpired (src/node.cpp:42-47) for the
+ * flat k-NN, the `good` snapshot of dhtgpu_find_closest at the scale of the whole set.  While a
+ * mask is set, dhtgpu_topk, dhtgpu_topk_dev, dhtgpu_batch_topk, dhtgpu_batch_topk_dev,
+ * dhtgpu_batch_topk_timed, dhtgpu_index_topk and dhtgpu_index_topk_dev return, per target, the k
+ * XOR-closest ACCEPTED ids: ascending, equal ids by lower original index, out_cnt = min(k,
+ * accepted), DHTGPU_NONE padded, and every index is that of the original set exactly as without a
+ * mask (+ idx_base; the global stream index on prefix shards per dhtgpu_set_global_indices; the
+ * same in record form, so dhtgpu_tie_words_dev and dhtgpu_merge*_dev need nothing new).  On a
+ * prefix shard the mask is indexed by shard-local position (dhtgpu_get_ids order).
+ *   The library keeps a live view: the accepted ids compacted in index order on the device (24 B
+ * per accepted id, 28 B on prefix shards), which the k-NN kernels answer from unchanged.  The
+ * setters only store bits and mark the view stale; the next k-NN call or dhtgpu_num_accepted
+ * rebuilds it once (one host synchronisation, whatever number of updates went before), so a
+ * stream-ordered caller calls dhtgpu_num_accepted outside its loop.  A mask that accepts every id
+ * builds no view (the unmasked path); one that rejects every id answers empty rows.  A view change
+ * drops what was built from the view: the sub-partitions of large sets (rebuilt by the next
+ * sub-partitioned call) and the view's K4 index (rebuilt by the next index query).  While a mask
+ * is set dhtgpu_sub_handles_active returns 0 and sub-partitioned calls return indices.
+ *   dhtgpu_set_ids / gen_ids / gen_ids_prefix clear the mask.  Unaffected -- they keep working on
+ * the full set, with their own masks where they have one: classify, cached_nodes, cache_*,
+ * buffer_nodes* (candidates are original indices, which is what masked lookups return),
+ * net_prepare / search_batch*, get_ids, ids_dev, select_prefix_dev.  Like dhtgpu_set_ids, the
+ * setters below are not to be called while k-NN calls of the context are in flight.
+ *
+ * accept[n] (host; nonzero = accepted; NULL = clear the mask: every id accepted again) */
+int dhtgpu_set_accept(dhtgpu_ctx* ctx, const uint8_t* accept);
+/* device bitmask, ceil(n/32) words, id i = bit (i & 31) of word i >> 5; bits past n ignored; copied
+ * stream-ordered */
+int dhtgpu_set_accept_bits_dev(dhtgpu_ctx* ctx, const uint32_t* bits, void* stream);
+/* flip m entries: accept[idx[j]] = val[j] (host arrays; idx < n else DHTGPU_EINVAL, nothing applied;
+ * distinct idx -- of a repeated one, one of its values holds).  With no mask set it starts from
+ * every id accepted. */
+int dhtgpu_update_accept(dhtgpu_ctx* ctx, const uint32_t* idx, const uint8_t* val, uint64_t m);
+/* ids currently accepted (n when no mask is set); brings the view up to date (may synchronise) */
+int dhtgpu_num_accepted(dhtgpu_ctx* ctx, uint64_t* out);
+/* overwrite ids [first, first+m) in place (slot reuse: mask a dead node off, write the new id into
+ * its slot, mask it on); first + m <= n else DHTGPU_ERANGE; prefix-shard contexts: DHTGPU_EINVAL.
+ * Keeps the mask; everything derived from the ids is rebuilt on its next use (the sorted / unique
+ * state at once; the lexicographic view, the K4 index, the sub-partitions, the view; the crawl
+ * model needs dhtgpu_net_prepare again). */
+int dhtgpu_write_ids(dhtgpu_ctx* ctx, uint64_t first, const uint8_t* ids20_be, uint64_t m);
 uint64_t dhtgpu_num_ids(const dhtgpu_ctx* ctx);
 /* Read back ids [first, first+n) as 20-byte big-endian. */
 int dhtgpu_get_ids(dhtgpu_ctx* ctx, uint64_t first, uint64_t n, uint8_t* out20_be);

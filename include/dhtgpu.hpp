@@ -304,6 +304,36 @@ public:
         for (size_t i = 0; i < n; ++i) detail::put_id(b, ids[i]);
         check(dhtgpu_set_ids(ctx_.get(), b.empty() ? nullptr : b.data(), n), "set_ids");
     }
+    /* Accept mask (Node::isGood / isExpired, src/node.cpp:42-47, for the resident set): while one
+     * is set, query() returns the closest ACCEPTED ids, as indices into the assigned array.
+     * accept[i] != 0 accepts id i; n must be the assigned size. */
+    void set_accept(const uint8_t* accept, size_t n) {
+        if (!accept || n != dhtgpu_num_ids(ctx_.get())) throw Error(DHTGPU_EINVAL, "set_accept: one byte per id");
+        check(dhtgpu_set_accept(ctx_.get(), accept), "set_accept");
+    }
+    void clear_accept() { check(dhtgpu_set_accept(ctx_.get(), nullptr), "set_accept"); }
+    /* accept[idx[j]] = val[j] for m entries (an expired node off, a revived one on) */
+    void update_accept(const uint32_t* idx, const uint8_t* val, size_t m) {
+        check(dhtgpu_update_accept(ctx_.get(), idx, val, m), "update_accept");
+    }
+    /* the snapshot rule of findClosestNodesBatch: id i is accepted when nodes[i] &&
+     * nodes[i]->isGood(now) (nodes[i] being the node whose id was assigned at i) */
+    template <class NodePtr, class TimePoint>
+    void set_accept_good(const std::vector<NodePtr>& nodes, TimePoint now) {
+        std::vector<uint8_t> a(nodes.size());
+        for (size_t i = 0; i < nodes.size(); ++i) a[i] = nodes[i] && nodes[i]->isGood(now) ? 1 : 0;
+        static const uint8_t none = 0;
+        set_accept(a.empty() ? &none : a.data(), a.size());
+    }
+    /* overwrite ids [first, first + m) in place (slot reuse: mask the dead node's slot off, write
+     * the new id into it, mask it on); the mask is kept */
+    template <class HashT>
+    void write(size_t first, const HashT* ids, size_t m) {
+        std::vector<uint8_t> b;
+        b.reserve(m * DHTGPU_HASH_LEN);
+        for (size_t i = 0; i < m; ++i) detail::put_id(b, ids[i]);
+        check(dhtgpu_write_ids(ctx_.get(), first, b.empty() ? nullptr : b.data(), m), "write_ids");
+    }
     /* out[i] = indices of the k ids closest to targets[i], ascending by XOR distance */
     template <class HashT>
     std::vector<std::vector<uint32_t>> query(const HashT* targets, size_t q, size_t k) const {

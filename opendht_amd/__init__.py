@@ -67,6 +67,11 @@ def lib():
         "dhtgpu_set_ids": ([_vp, _u8p, ctypes.c_uint64], ctypes.c_int),
         "dhtgpu_gen_ids": ([_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
         "dhtgpu_num_ids": ([_vp], ctypes.c_uint64),
+        "dhtgpu_set_accept": ([_vp, _u8p], ctypes.c_int),
+        "dhtgpu_set_accept_bits_dev": ([_vp, _vp, _vp], ctypes.c_int),
+        "dhtgpu_update_accept": ([_vp, _u32p, _u8p, ctypes.c_uint64], ctypes.c_int),
+        "dhtgpu_num_accepted": ([_vp, _u64p], ctypes.c_int),
+        "dhtgpu_write_ids": ([_vp, ctypes.c_uint64, _u8p, ctypes.c_uint64], ctypes.c_int),
         "dhtgpu_set_global_indices": ([_vp, ctypes.c_int], ctypes.c_int),
         "dhtgpu_set_sub_handles": ([_vp, ctypes.c_int], ctypes.c_int),
         "dhtgpu_sub_handles_active": ([_vp, ctypes.c_uint32, ctypes.c_uint32], ctypes.c_int),
@@ -130,6 +135,8 @@ def lib():
                                      _vp, _vp, _vp, _vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
+        if os.environ.get("DHTGPU_LIB") and not hasattr(L, name):
+            continue   # an A/B build of an earlier commit (yardstick runs): calling the entry raises
         f = getattr(L, name)
         f.argtypes = args
         f.restype = res
@@ -151,7 +158,8 @@ def exported_symbols():
             "dhtgpu_search_batch", "dhtgpu_search_batch_dev", "dhtgpu_set_global_indices", "dhtgpu_set_sub_handles",
             "dhtgpu_sub_handles_active", "dhtgpu_handles_to_indices_dev", "dhtgpu_set_search_alpha", "dhtgpu_cache_set",
             "dhtgpu_cache_nodes", "dhtgpu_cache_sorted", "dhtgpu_buffer_nodes_ids", "dhtgpu_batch_events",
-            "dhtgpu_search_insert", "dhtgpu_table_stats"]
+            "dhtgpu_search_insert", "dhtgpu_table_stats", "dhtgpu_set_accept", "dhtgpu_set_accept_bits_dev",
+            "dhtgpu_update_accept", "dhtgpu_num_accepted", "dhtgpu_write_ids"]
 
 
 def _ids(a, name="ids"):
@@ -239,6 +247,41 @@ class Context:
         _check(lib().dhtgpu_select_prefix_dev(self._h, planes_ptr, stride, n, pbits, pval, out_planes_ptr, out_stride,
                                               out_gidx_ptr, ctypes.byref(cnt), stream), "select_prefix_dev")
         return cnt.value
+
+    # ---- accept mask (Node::isGood for the flat k-NN) --------------------------
+    def set_accept(self, mask):
+        """(n,) bool/uint8 mask over the id set (nonzero = accepted), or None to clear it.  While a
+        mask is set topk / index_topk / batch_topk (and their _dev forms) answer from the accepted
+        ids only; indices stay those of the original set."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            if m.shape[0] != self.num_ids:
+                raise ValueError("accept mask must have one byte per id")
+        _check(lib().dhtgpu_set_accept(self._h, _p(m, _u8p) if m is not None else None), "set_accept")
+
+    def set_accept_bits_dev(self, bits_ptr, stream=None):
+        """Device bitmask of ceil(n/32) uint32 words (id i = bit i & 31 of word i >> 5), copied
+        stream-ordered."""
+        _check(lib().dhtgpu_set_accept_bits_dev(self._h, bits_ptr, stream), "set_accept_bits_dev")
+
+    def update_accept(self, idx, val):
+        """accept[idx[j]] = val[j] (val: array or one value for all)."""
+        i = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(val), i.shape)).astype(np.uint8).reshape(-1)
+        _check(lib().dhtgpu_update_accept(self._h, _p(i, _u32p), _p(v, _u8p), i.shape[0]), "update_accept")
+
+    @property
+    def num_accepted(self):
+        """Ids currently accepted (brings the mask's view up to date)."""
+        out = ctypes.c_uint64()
+        _check(lib().dhtgpu_num_accepted(self._h, ctypes.byref(out)), "num_accepted")
+        return int(out.value)
+
+    def write_ids(self, first, ids):
+        """Overwrite ids [first, first + len(ids)) in place (slot reuse); keeps the mask."""
+        ids = _ids(ids)
+        _check(lib().dhtgpu_write_ids(self._h, int(first), _p(ids, _u8p), ids.shape[0]), "write_ids")
 
     @property
     def num_ids(self):

@@ -160,6 +160,46 @@ struct dhtgpu_ctx {
     hipEvent_t next_ev[8] = {};   // dhtgpu_batch_events: the next K6 call records its kernels here
     bool has_next_ev = false;
     DevBuf stamps;
+    // Accept mask (dhtgpu_set_accept ...): a bitmask over the set and its live view -- the accepted
+    // ids compacted in index order into planes of their own, with the view -> set index map.  The
+    // setters store bits and mark the view stale; the next k-NN call (or dhtgpu_num_accepted)
+    // rebuilds it once (view.hip).  The k-NN paths read the set through active_set(): the view when
+    // a mask rejects at least one id, else the set itself.
+    struct Accept {
+        DevBuf bits;             // view_mask_words(stride) words, zero past n
+        bool has_mask = false;
+        bool stale = false;      // bits changed (or the ids did) since the view was built
+        hipStream_t bits_stream = nullptr;   // dhtgpu_set_accept_bits_dev: the stream its copy is ordered on
+        bool active = false;     // the view is in use: a mask is set and rejects at least one id
+        DevBuf planes, map, w0s, gmap;   // 5 * stride u32; view -> set; shifted word 0; view -> global stream
+        uint64_t n = 0, stride = 0;
+        DevBuf bmap;             // map + bmap_base (a plain context's idx_base != 0), built on first use
+        uint32_t bmap_base = 0;
+        bool bmap_valid = false;
+        DevBuf index;            // the view's own K4 index (the set's stays valid for the crawl model)
+        uint32_t index_B = 0;
+        bool index_valid = false;
+        DevBuf toff;             // tile offsets + total (build scratch)
+    } acc;
+    // What a k-NN call answers from: the id set, or the accept mask's view of it.
+    struct ActiveSet {
+        const uint32_t* planes; uint64_t stride, n;
+        const uint32_t* map;     // result index map (nullable: index + idx_base); a view's carries idx_base
+        const uint32_t* w0s;     // prefix shard: shifted word-0 plane (else nullptr)
+        uint32_t pbits, pval;    // prefix shard: shard_pbits / shard_pval
+        bool view;
+        DevBuf* index; uint32_t* index_B; bool* index_valid;   // the K4 index over these ids
+    };
+    int active_set(uint32_t idx_base, ActiveSet* out);   // brings the view up to date (may synchronise)
+    void clear_accept() {
+        const bool was = acc.active;
+        acc.has_mask = acc.stale = acc.active = false;
+        acc.bmap_valid = acc.index_valid = false;
+        acc.n = 0;
+        for (DevBuf* b : {&acc.planes, &acc.map, &acc.w0s, &acc.gmap, &acc.bmap, &acc.index, &acc.toff, &acc.bits})
+            b->release();
+        if (was) invalidate_subs();   // they were built from the view
+    }
 
     hipError_t bind() { return hipSetDevice(device); }
     void invalidate_subs() {
@@ -186,6 +226,89 @@ struct dhtgpu_ctx {
         return hipSuccess;
     }
 };
+
+// Rebuild the accept mask's view when its bits (or the ids under it) changed: count (V1 + V2, one
+// host sync for the total, which sizes every view buffer), then the compaction (V3).  The view
+// meets what the kernels assume of an id set: stride pad_ids(n), zeroed padding, w0s of the full
+// stride.  A mask that accepts every id builds no view.  Everything derived from the previous view
+// (sub-partitions, the view's index, the fallback hint, the idx_base map) is dropped.
+static int ensure_view(dhtgpu_ctx* c) {
+    dhtgpu_ctx::Accept& a = c->acc;
+    if (!a.has_mask || !a.stale) return DHTGPU_OK;
+    hipStream_t s = c->stream;
+    if (a.bits_stream && a.bits_stream != s) DHT_TRY(hipStreamSynchronize(a.bits_stream));
+    a.bits_stream = nullptr;
+    const uint64_t ntiles = c->stride / kTile;
+    DHT_TRY(a.toff.ensure((size_t)(ntiles + 4) * 4 + 16));
+    unsigned long long* d_total = a.toff.as<unsigned long long>();
+    uint32_t* toff = a.toff.as<uint32_t>() + 4;
+    DHT_TRY(launch_view_count(a.bits.as<uint32_t>(), c->stride, toff, d_total, s));
+    unsigned long long m = 0;
+    DHT_TRY(hipMemcpyAsync(&m, d_total, 8, hipMemcpyDeviceToHost, s));
+    DHT_TRY(hipStreamSynchronize(s));
+    const bool was = a.active;
+    a.active = false;   // (until the new view stands)
+    a.bmap_valid = false;
+    a.index_valid = false;
+    if (was || m < c->n) c->invalidate_subs();
+    if (m > c->n) return DHTGPU_EDEVICE;   // (bits past n are cleared by every setter)
+    a.n = m;
+    if (m < c->n) {
+        a.stride = pad_ids(m ? m : 1);
+        const bool shard = c->shard_pbits != 0, glob = c->has_gidx;
+        DHT_TRY(a.planes.ensure((size_t)a.stride * 5 * 4));
+        DHT_TRY(a.map.ensure((size_t)a.stride * 4));
+        if (shard) DHT_TRY(a.w0s.ensure((size_t)a.stride * 4));
+        if (glob) DHT_TRY(a.gmap.ensure((size_t)a.stride * 4));
+        for (int w = 0; w < 5; ++w)
+            DHT_TRY(launch_fill(a.planes.as<uint32_t>() + (uint64_t)w * a.stride + m, a.stride - m, 0u, s));
+        if (shard) DHT_TRY(launch_fill(a.w0s.as<uint32_t>() + m, a.stride - m, 0u, s));
+        if (m)
+            DHT_TRY(launch_view_compact(c->planes.as<uint32_t>(), c->stride, a.bits.as<uint32_t>(), toff,
+                                        a.planes.as<uint32_t>(), a.stride, a.map.as<uint32_t>(),
+                                        shard ? a.w0s.as<uint32_t>() : nullptr, c->shard_pbits,
+                                        glob ? c->gidx.as<uint32_t>() : nullptr, glob ? a.gmap.as<uint32_t>() : nullptr, s));
+        DHT_TRY(hipStreamSynchronize(s));   // calls on other streams read the view
+        a.active = true;
+    }
+    a.stale = false;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_ctx::active_set(uint32_t idx_base, ActiveSet* out) {
+    int r = ensure_view(this);
+    if (r) return r;
+    if (!acc.active) {
+        *out = ActiveSet{planes.as<uint32_t>(), stride, n, out_map(), shard_pbits ? w0s.as<uint32_t>() : nullptr,
+                         shard_pbits, shard_pval, false, &index, &index_B, &index_valid};
+        return DHTGPU_OK;
+    }
+    const uint32_t* m = acc.map.as<uint32_t>();
+    if (has_gidx && map_global) {
+        m = acc.gmap.as<uint32_t>();
+    } else if (idx_base) {   // a map and an offset at once: map + idx_base, cached per base
+        if (!acc.bmap_valid || acc.bmap_base != idx_base) {
+            acc.bmap_valid = false;
+            DHT_TRY(acc.bmap.ensure((size_t)acc.stride * 4));
+            DHT_TRY(launch_view_add(acc.map.as<uint32_t>(), acc.n, idx_base, acc.bmap.as<uint32_t>(), stream));
+            DHT_TRY(hipStreamSynchronize(stream));   // read by calls on any stream
+            acc.bmap_base = idx_base;
+            acc.bmap_valid = true;
+        }
+        m = acc.bmap.as<uint32_t>();
+    }
+    *out = ActiveSet{acc.planes.as<uint32_t>(), acc.stride, acc.n, m, shard_pbits ? acc.w0s.as<uint32_t>() : nullptr,
+                     shard_pbits, shard_pval, true, &acc.index, &acc.index_B, &acc.index_valid};
+    return DHTGPU_OK;
+}
+
+// an all-rejected mask: every row empty (stream-ordered)
+static int answer_empty(uint32_t q, uint32_t k, uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, hipStream_t s) {
+    if (out_idx) DHT_TRY(launch_fill(out_idx, (uint64_t)q * k, DHTGPU_NONE, s));
+    if (out_cnt) DHT_TRY(launch_fill(out_cnt, q, 0u, s));
+    if (out_rec) DHT_TRY(launch_fill(out_rec, (uint64_t)q * k * 3, DHTGPU_NONE, s));
+    return DHTGPU_OK;
+}
 
 extern "C" {
 
@@ -258,6 +381,7 @@ void dhtgpu_ctx_destroy(dhtgpu_ctx* c) {
         b->release();
     for (auto& b : c->bslot)
         for (DevBuf* d : {&b.ws, &b.out_idx, &b.out_cnt, &b.sws}) d->release();
+    c->clear_accept();
     c->invalidate_subs();
     if (c->fb_hint) (void)hipHostFree(c->fb_hint);
     for (DevBuf* b : {&c->stamps, &c->w0s, &c->sview.planes, &c->sview.perm,
@@ -296,6 +420,7 @@ static int alloc_ids(dhtgpu_ctx* c, uint64_t n) {
     c->shard_pbits = 0;
     c->shard_pval = 0;
     c->has_gidx = false;
+    c->clear_accept();   // a new id set: every id accepted
     c->invalidate_subs();
     c->sview.valid = false;
     c->stride = pad_ids(n ? n : 1);
@@ -379,7 +504,7 @@ int dhtgpu_set_sub_handles(dhtgpu_ctx* c, int on) {
     return DHTGPU_OK;
 }
 
-static bool needs_subs(const dhtgpu_ctx* c, uint32_t q, uint32_t k);
+static bool needs_subs(const dhtgpu_ctx* c, uint64_t n, uint32_t q, uint32_t k);
 
 // measurement only (not in include/): the phase-stamp buffer of DHTGPU_DBG=256 runs
 int dhtgpu_debug_stamps(dhtgpu_ctx* c, void** dev_ptr, uint64_t* bytes) {
@@ -389,9 +514,125 @@ int dhtgpu_debug_stamps(dhtgpu_ctx* c, void** dev_ptr, uint64_t* bytes) {
     return 0;
 }
 
+// ---- accept mask ----------------------------------------------------------------------------
+// the mask buffer at the size the view kernels read unchecked, all zero
+static int mask_alloc(dhtgpu_ctx* c, hipStream_t s) {
+    const size_t bytes = (size_t)view_mask_words(c->stride) * 4;
+    DHT_TRY(c->acc.bits.ensure(bytes));
+    DHT_TRY(hipMemsetAsync(c->acc.bits.p, 0, bytes, s));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_set_accept(dhtgpu_ctx* c, const uint8_t* accept) {
+    if (!c) return DHTGPU_EINVAL;
+    if (!c->has_ids) return DHTGPU_ENOIDS;
+    DHT_TRY(c->bind());
+    if (!accept) {   // every id accepted again: the view and what was built from it go
+        DHT_TRY(hipStreamSynchronize(c->stream));
+        c->clear_accept();
+        return DHTGPU_OK;
+    }
+    hipStream_t s = c->stream;
+    int r = mask_alloc(c, s);
+    if (r) return r;
+    // bytes -> bits on the device, 2^22 ids of staging at a time (whole mask words per chunk)
+    const uint64_t chunk = 1ull << 22;
+    DHT_TRY(c->staging.ensure((size_t)std::min<uint64_t>(c->stride, chunk)));
+    for (uint64_t i = 0; i < c->n; i += chunk) {
+        const uint64_t m = std::min(chunk, c->n - i), words = (m + 31) / 32;
+        if (m < words * 32) DHT_TRY(hipMemsetAsync(c->staging.as<uint8_t>() + m, 0, (size_t)(words * 32 - m), s));
+        DHT_TRY(hipMemcpyAsync(c->staging.p, accept + i, (size_t)m, hipMemcpyHostToDevice, s));
+        DHT_TRY(launch_view_pack(c->staging.as<uint8_t>(), words, c->acc.bits.as<uint32_t>() + i / 32, s));
+        DHT_TRY(hipStreamSynchronize(s));   // staging is reused; accept[] is the caller's again
+    }
+    c->acc.bits_stream = nullptr;
+    c->acc.has_mask = true;
+    c->acc.stale = true;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_set_accept_bits_dev(dhtgpu_ctx* c, const uint32_t* bits, void* stream) {
+    if (!c || !bits) return DHTGPU_EINVAL;
+    if (!c->has_ids) return DHTGPU_ENOIDS;
+    DHT_TRY(c->bind());
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int r = mask_alloc(c, s);
+    if (r) return r;
+    DHT_TRY(hipMemcpyAsync(c->acc.bits.p, bits, (size_t)((c->n + 31) / 32) * 4, hipMemcpyDeviceToDevice, s));
+    DHT_TRY(launch_view_trim(c->acc.bits.as<uint32_t>(), c->n, s));
+    c->acc.bits_stream = s;   // the rebuild waits for this copy
+    c->acc.has_mask = true;
+    c->acc.stale = true;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_update_accept(dhtgpu_ctx* c, const uint32_t* idx, const uint8_t* val, uint64_t m) {
+    if (!c || (m && (!idx || !val))) return DHTGPU_EINVAL;
+    if (!c->has_ids) return DHTGPU_ENOIDS;
+    for (uint64_t j = 0; j < m; ++j)
+        if (idx[j] >= c->n) return DHTGPU_EINVAL;   // nothing applied
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    hipStream_t s = c->stream;
+    if (c->acc.bits_stream && c->acc.bits_stream != s) DHT_TRY(hipStreamSynchronize(c->acc.bits_stream));
+    c->acc.bits_stream = nullptr;
+    if (!c->acc.has_mask) {   // no mask yet: start from every id accepted
+        int r = mask_alloc(c, s);
+        if (r) return r;
+        DHT_TRY(launch_fill(c->acc.bits.as<uint32_t>(), (c->n + 31) / 32, 0xFFFFFFFFu, s));
+        DHT_TRY(launch_view_trim(c->acc.bits.as<uint32_t>(), c->n, s));
+    }
+    const size_t ib = al256((size_t)m * 4);
+    DHT_TRY(c->staging.ensure(ib + (size_t)m));
+    DHT_TRY(hipMemcpyAsync(c->staging.p, idx, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    DHT_TRY(hipMemcpyAsync(c->staging.as<uint8_t>() + ib, val, (size_t)m, hipMemcpyHostToDevice, s));
+    DHT_TRY(launch_view_update(c->acc.bits.as<uint32_t>(), c->staging.as<uint32_t>(), c->staging.as<uint8_t>() + ib, m, s));
+    DHT_TRY(hipStreamSynchronize(s));   // idx / val are the caller's again
+    c->acc.has_mask = true;
+    c->acc.stale = true;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_num_accepted(dhtgpu_ctx* c, uint64_t* out) {
+    if (!c || !out) return DHTGPU_EINVAL;
+    if (!c->has_ids) return DHTGPU_ENOIDS;
+    DHT_TRY(c->bind());
+    int r = ensure_view(c);
+    if (r) return r;
+    *out = c->acc.active ? c->acc.n : c->n;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_write_ids(dhtgpu_ctx* c, uint64_t first, const uint8_t* ids20, uint64_t m) {
+    if (!c || (!ids20 && m)) return DHTGPU_EINVAL;
+    if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (c->has_gidx) return DHTGPU_EINVAL;   // a prefix shard's ids share its prefix
+    if (first > c->n || m > c->n - first) return DHTGPU_ERANGE;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    // everything derived from the ids goes: the lexicographic view, both K4 indices, the
+    // sub-partitions, the crawl model and the mask's view (the mask itself stays)
+    c->sview.valid = false;
+    c->index_valid = false;
+    c->acc.index_valid = false;
+    c->net_valid = false;
+    c->invalidate_subs();
+    if (c->acc.has_mask) c->acc.stale = true;
+    const uint64_t chunk = 1ull << 22;
+    DHT_TRY(c->staging.ensure((size_t)std::min<uint64_t>(m, chunk) * 20));
+    for (uint64_t i = 0; i < m; i += chunk) {
+        const uint64_t mm = std::min(chunk, m - i);
+        DHT_TRY(hipMemcpyAsync(c->staging.p, ids20 + i * 20, (size_t)mm * 20, hipMemcpyHostToDevice, c->stream));
+        DHT_TRY(launch_pack(c->staging.as<uint8_t>(), mm, c->planes.as<uint32_t>() + first + i, c->stride, c->stream));
+        DHT_TRY(hipStreamSynchronize(c->stream));   // staging is reused
+    }
+    return finish_ids(c, c->n);   // (padding untouched) the sorted / unique flag again
+}
+
 int dhtgpu_sub_handles_active(dhtgpu_ctx* c, uint32_t q, uint32_t k) {
     if (!c || !c->has_ids) return 0;
-    return c->sub_handles && !(small_supported(c->n, q, k) && !(c->dbg & (1u << 23))) && needs_subs(c, q, k) ? 1 : 0;
+    if (c->acc.has_mask) return 0;   // masked calls return indices
+    return c->sub_handles && !(small_supported(c->n, q, k) && !(c->dbg & (1u << 23))) && needs_subs(c, c->n, q, k) ? 1 : 0;
 }
 
 int dhtgpu_handles_to_indices_dev(dhtgpu_ctx* c, const uint32_t* handles, uint64_t m, uint32_t* out_idx,
@@ -458,12 +699,14 @@ int dhtgpu_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, 
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const ScanPlan p = plan_scan(c->n, q, k, c->num_cus);
-    const uint32_t* gidx = c->out_map();
-    const bool one = p.splits == 1 || c->n == 0;
+    dhtgpu_ctx::ActiveSet A;
+    if (int r = c->active_set(idx_base, &A)) return r;
+    if (A.view && !A.n) return answer_empty(q, k, out_idx, out_cnt, out_rec, s);
+    const ScanPlan p = plan_scan(A.n, q, k, c->num_cus);
+    const uint32_t* gidx = A.map;
+    const bool one = p.splits == 1 || A.n == 0;
     if (one && !out_rec) {   // one pass writes the final form directly
-        DHT_TRY(launch_scan(c->planes.as<uint32_t>(), c->stride, c->n, p, tp, ts, q, k, out_idx, out_cnt, out_rec,
-                            gidx, idx_base, s));
+        DHT_TRY(launch_scan(A.planes, A.stride, A.n, p, tp, ts, q, k, out_idx, out_cnt, out_rec, gidx, idx_base, s));
         return DHTGPU_OK;
     }
     // local indices (merged over id-range splits when the batch is too small to fill the
@@ -477,16 +720,15 @@ int dhtgpu_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, 
         lc = c->out_cnt.as<uint32_t>();
     }
     if (one) {
-        DHT_TRY(launch_scan(c->planes.as<uint32_t>(), c->stride, c->n, p, tp, ts, q, k, li, lc, nullptr, nullptr, 0,
-                            s));
+        DHT_TRY(launch_scan(A.planes, A.stride, A.n, p, tp, ts, q, k, li, lc, nullptr, nullptr, 0, s));
     } else {
         DHT_TRY(c->rec.ensure((size_t)p.splits * q * k * 6 * 4));
-        DHT_TRY(launch_scan(c->planes.as<uint32_t>(), c->stride, c->n, p, tp, ts, q, k, nullptr, nullptr,
-                            c->rec.as<uint32_t>(), nullptr, 0, s));
+        DHT_TRY(launch_scan(A.planes, A.stride, A.n, p, tp, ts, q, k, nullptr, nullptr, c->rec.as<uint32_t>(), nullptr, 0,
+                            s));
         DHT_TRY(launch_merge(c->rec.as<uint32_t>(), p.splits, q, k, tp, ts, k, li, lc, s));
     }
     if (out_rec)
-        DHT_TRY(launch_rec3(li, (uint64_t)q * k, c->planes.as<uint32_t>(), c->stride, idx_base, gidx, out_rec, s));
+        DHT_TRY(launch_rec3(li, (uint64_t)q * k, A.planes, A.stride, idx_base, gidx, out_rec, s));
     else
         DHT_TRY(launch_map_idx(li, (uint64_t)q * k, gidx, idx_base, s));
     return DHTGPU_OK;
@@ -567,17 +809,26 @@ int dhtgpu_topk(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, uint3
     return DHTGPU_OK;
 }
 
+// the K4 index over an active set (the id set's own index, or the view's)
+static int index_build_on(const dhtgpu_ctx::ActiveSet& A, hipStream_t s, hipEvent_t* ev) {
+    const uint32_t B = index_bits(A.n);
+    *A.index_valid = false;
+    DHT_TRY(A.index->ensure(index_bytes(A.n, B)));
+    DHT_TRY(launch_index_build(A.planes, A.stride, A.n, B, A.index->p, s, ev));
+    *A.index_B = B;
+    *A.index_valid = true;
+    return DHTGPU_OK;
+}
+
 int dhtgpu_index_build(dhtgpu_ctx* c, void* stream) {
     if (!c) return DHTGPU_EINVAL;
     if (!c->has_ids) return DHTGPU_ENOIDS;
     DHT_TRY(c->bind());
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const uint32_t B = index_bits(c->n);
-    DHT_TRY(c->index.ensure(index_bytes(c->n, B)));
-    DHT_TRY(launch_index_build(c->planes.as<uint32_t>(), c->stride, c->n, B, c->index.p, s));
-    c->index_B = B;
-    c->index_valid = true;
-    return DHTGPU_OK;
+    dhtgpu_ctx::ActiveSet A;
+    if (int r = c->active_set(0, &A)) return r;
+    if (A.view && !A.n) return DHTGPU_OK;   // every id rejected: queries answer empty rows
+    return index_build_on(A, s, nullptr);
 }
 
 int dhtgpu_index_build_timed(dhtgpu_ctx* c, void* stream, float* ms4) {
@@ -585,17 +836,16 @@ int dhtgpu_index_build_timed(dhtgpu_ctx* c, void* stream, float* ms4) {
     if (!c->has_ids) return DHTGPU_ENOIDS;
     DHT_TRY(c->bind());
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const uint32_t B = index_bits(c->n);
-    DHT_TRY(c->index.ensure(index_bytes(c->n, B)));
+    dhtgpu_ctx::ActiveSet A;
+    if (int r = c->active_set(0, &A)) return r;
     hipEvent_t ev[5];
     for (int i = 0; i < 5; ++i) DHT_TRY(hipEventCreate(&ev[i]));
-    hipError_t e = launch_index_build(c->planes.as<uint32_t>(), c->stride, c->n, B, c->index.p, s, ev);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[4]);
-    for (int i = 0; e == hipSuccess && i < 4; ++i) e = hipEventElapsedTime(&ms4[i], ev[i], ev[i + 1]);
+    int r = index_build_on(A, s, ev);
+    hipError_t e = r ? hipSuccess : hipEventSynchronize(ev[4]);
+    for (int i = 0; !r && e == hipSuccess && i < 4; ++i) e = hipEventElapsedTime(&ms4[i], ev[i], ev[i + 1]);
     for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]);
+    if (r) return r;
     DHT_TRY(e);
-    c->index_B = B;
-    c->index_valid = true;
     return DHTGPU_OK;
 }
 
@@ -604,11 +854,19 @@ int dhtgpu_index_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
                           void* stream) {
     if (!c || k == 0 || k > DHTGPU_MAX_K || (q && !tp)) return DHTGPU_EINVAL;
     if (!out_rec && (!out_idx || !out_cnt)) return DHTGPU_EINVAL;
-    if (!c->has_ids || !c->index_valid) return DHTGPU_ENOIDS;
+    if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (!c->acc.has_mask && !c->index_valid) return DHTGPU_ENOIDS;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const uint32_t* gidx = c->out_map();
+    dhtgpu_ctx::ActiveSet A;
+    if (int r = c->active_set(idx_base, &A)) return r;
+    if (A.view && !A.n) return answer_empty(q, k, out_idx, out_cnt, out_rec, s);
+    if (!*A.index_valid) {   // under a mask the index is built by its first query (stream-ordered, on s)
+        if (!c->acc.has_mask) return DHTGPU_ENOIDS;
+        if (int r = index_build_on(A, s, nullptr)) return r;
+    }
+    const uint32_t* gidx = A.map;
     uint32_t* li = out_idx;
     uint32_t* lc = out_cnt;
     if (out_rec) {   // candidate records for a cross-shard merge
@@ -617,10 +875,9 @@ int dhtgpu_index_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
         li = c->out_idx.as<uint32_t>();
         lc = c->out_cnt.as<uint32_t>();
     }
-    DHT_TRY(launch_index_query(c->index.p, c->n, c->index_B, c->planes.as<uint32_t>(), c->stride, tp, ts, q, k,
-                               li, lc, s));
+    DHT_TRY(launch_index_query(A.index->p, A.n, *A.index_B, A.planes, A.stride, tp, ts, q, k, li, lc, s));
     if (out_rec)
-        DHT_TRY(launch_rec3(li, (uint64_t)q * k, c->planes.as<uint32_t>(), c->stride, idx_base, gidx, out_rec, s));
+        DHT_TRY(launch_rec3(li, (uint64_t)q * k, A.planes, A.stride, idx_base, gidx, out_rec, s));
     else
         DHT_TRY(launch_map_idx(li, (uint64_t)q * k, gidx, idx_base, s));
     return DHTGPU_OK;
@@ -632,7 +889,7 @@ int dhtgpu_index_topk(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k,
     if (!c->has_ids) return DHTGPU_ENOIDS;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
-    if (!c->index_valid) {
+    if (!c->acc.has_mask && !c->index_valid) {   // (a view's index: built by the query below)
         int r = dhtgpu_index_build(c, c->stream);
         if (r) return r;
     }
@@ -725,22 +982,22 @@ static int batch_slot_run(dhtgpu_ctx* c, int si, BatchCall bc, hipStream_t s, hi
 // prefix range, so its survivors fall into a few partitions (long, coalesced bucket runs instead
 // of a few entries in every partition) and a partition's survivors, results and result-map
 // entries sit in a narrow index window (F3's gathers and record words hit lines they share).
-static int build_subs(dhtgpu_ctx* c, bool sort) {
+static int build_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, bool sort) {
     if (c->subs_valid) return DHTGPU_OK;
     c->invalidate_subs();
     uint32_t sb = 1;
-    while (sb < 8 && (c->n >> sb) > (1ull << 24)) ++sb;
-    const uint32_t P = c->shard_pbits + sb;   // prefix bits every id of a sub-partition shares
+    while (sb < 8 && (A.n >> sb) > (1ull << 24)) ++sb;
+    const uint32_t P = A.pbits + sb;   // prefix bits every id of a sub-partition shares
     if (P > 24) return DHTGPU_ERANGE;
     hipStream_t s = c->stream;
-    DHT_TRY(c->aux.ensure((size_t)select_scratch_words(c->n) * 4 + 16));
+    DHT_TRY(c->aux.ensure((size_t)select_scratch_words(A.n) * 4 + 16));
     unsigned long long* d_total = reinterpret_cast<unsigned long long*>(c->aux.as<uint8_t>());
     uint32_t* scratch = reinterpret_cast<uint32_t*>(c->aux.as<uint8_t>() + 8);
-    const uint32_t* planes = c->planes.as<uint32_t>();
+    const uint32_t* planes = A.planes;   // (a view: "context-local" below is the view's index)
     c->subs.resize((size_t)1 << sb);
     for (uint32_t i = 0; i < (1u << sb); ++i) {
-        const uint32_t pv = (c->shard_pval << sb) | i;
-        DHT_TRY(launch_select_prefix(planes, c->stride, c->n, P, pv, scratch, d_total, nullptr, 0, nullptr, 0, s));
+        const uint32_t pv = (A.pval << sb) | i;
+        DHT_TRY(launch_select_prefix(planes, A.stride, A.n, P, pv, scratch, d_total, nullptr, 0, nullptr, 0, s));
         unsigned long long m = 0;
         DHT_TRY(hipMemcpyAsync(&m, d_total, 8, hipMemcpyDeviceToHost, s));
         DHT_TRY(hipStreamSynchronize(s));
@@ -752,7 +1009,7 @@ static int build_subs(dhtgpu_ctx* c, bool sort) {
         DHT_TRY(sp.w0s.ensure((size_t)sp.stride * 4));
         for (int w = 0; w < 5; ++w)   // deterministic padding words (F2 may read them, masked)
             DHT_TRY(launch_fill(sp.planes.as<uint32_t>() + (uint64_t)w * sp.stride + m, sp.stride - m, 0u, s));
-        DHT_TRY(launch_select_prefix(planes, c->stride, c->n, P, pv, scratch, d_total, sp.planes.as<uint32_t>(),
+        DHT_TRY(launch_select_prefix(planes, A.stride, A.n, P, pv, scratch, d_total, sp.planes.as<uint32_t>(),
                                      sp.stride, sp.map.as<uint32_t>(), 0, s));
         if (sort && m > 1) {   // prefix order (stable sort of the compacted ids; perm -> context-local map)
             DevBuf sorted, perm, sscr;
@@ -778,7 +1035,7 @@ static int build_subs(dhtgpu_ctx* c, bool sort) {
         if (c->has_gidx) {   // sub -> global stream index, composed once
             DHT_TRY(sp.gmap.ensure((size_t)sp.stride * 4));
             DHT_TRY(hipMemcpyAsync(sp.gmap.p, sp.map.p, (size_t)m * 4, hipMemcpyDeviceToDevice, s));
-            DHT_TRY(launch_map_idx(sp.gmap.as<uint32_t>(), m, c->gidx.as<uint32_t>(), 0, s));
+            DHT_TRY(launch_map_idx(sp.gmap.as<uint32_t>(), m, A.view ? c->acc.gmap.as<uint32_t>() : c->gidx.as<uint32_t>(), 0, s));
         }
     }
     // level-cell_level() id counts of every sub-partition (sibling marking, BatchCall::cells)
@@ -832,7 +1089,7 @@ static int build_subs(dhtgpu_ctx* c, bool sort) {
 // outside it, so its top-k is the set's.  Targets whose sub-partition is short of k ids (or
 // whose partition overflowed) take F4's scan over the whole set.  A split K6 cannot plan
 // (strongly clustered ids: one sub-partition far above 2^24) takes the K1 scan.
-static int batch_run_subs(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k, uint32_t* out_idx,
+static int batch_run_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k, uint32_t* out_idx,
                           uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base, hipStream_t s, hipEvent_t* ev) {
     // Prefix-sorted sub-partitions: an F2 range's survivors fall into a few partitions that the
     // range owns, so F2 writes them straight to their buckets with no stage (k_f2_direct: a few KB
@@ -845,23 +1102,23 @@ static int batch_run_subs(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
     bool sort = false;
     {
         uint32_t sbe = 1;
-        while (sbe < 8 && (c->n >> sbe) > (1ull << 24)) ++sbe;
-        const uint64_t nsub_e = c->n >> sbe;
+        while (sbe < 8 && (A.n >> sbe) > (1ull << 24)) ++sbe;
+        const uint64_t nsub_e = A.n >> sbe;
         const double qsub = (double)q / (double)(1u << sbe);
         uint32_t lm = 0;
         while (lm < 19 && (nsub_e >> (lm + 1)) >= 4ull * k) ++lm;
         lm = lm + 1 < 19 ? lm + 1 : 19;
         sort = 1.0 - std::exp(-qsub / (double)(1ull << lm)) > 0.02;
     }
-    int r = build_subs(c, sort);
+    int r = build_subs(c, A, sort);
     if (r) return r;
     const uint32_t sb = c->sub_bits, S = 1u << sb;
     const uint32_t pf = kPlanCells | (c->subs_sorted ? kPlanSorted : 0u);
-    const uint32_t P = c->shard_pbits + sb;
+    const uint32_t P = A.pbits + sb;
     const uint32_t q_plan = std::max<uint32_t>(1u, (uint32_t)(((uint64_t)q + S - 1) >> sb));
     uint64_t n_max = 0;
     for (const auto& sp : c->subs) n_max = std::max<uint64_t>(n_max, sp.n);
-    const bool handles = c->sub_handles && !out_rec;
+    const bool handles = c->sub_handles && !out_rec && !c->acc.has_mask;   // (masked calls return indices)
     if (!batch_supported(n_max, q_plan, k, c->num_cus, S, pf)) {
         if (!handles) return dhtgpu_topk_dev(c, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s);
         // handles on the K1 route: context-local indices, then their handles
@@ -895,20 +1152,20 @@ static int batch_run_subs(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
         off += sp.n;
     }
     BatchCall bc{};
-    bc.planes = c->planes.as<uint32_t>();   // F4's scan: the whole set
-    bc.stride = c->stride;
-    bc.n = c->n;
+    bc.planes = A.planes;   // F4's scan: the whole set
+    bc.stride = A.stride;
+    bc.n = A.n;
     bc.tp = tp;
     bc.ts = ts;
     bc.q = q;
     bc.q_plan = q_plan;
     bc.k = k;
     bc.skip = P;
-    bc.pval = c->shard_pval;
+    bc.pval = A.pval;
     bc.cells = c->cells.as<uint8_t>();
     bc.spans = c->spans.empty() ? nullptr : c->spans.data();
     bc.sorted = c->subs_sorted ? 1u : 0u;
-    bc.gidx = global ? c->gidx.as<uint32_t>() : nullptr;
+    bc.gidx = global ? A.map : nullptr;
     bc.base = 0;
     bc.out_idx = li;
     bc.out_cnt = lc;
@@ -917,10 +1174,10 @@ static int batch_run_subs(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
     bc.ev = ev;
     bc.subs = specs.data();
     bc.nsub = S;
-    bc.sub_shift = c->shard_pbits;
+    bc.sub_shift = A.pbits;
     bc.sub_bits = sb;
     bc.out_rec = out_rec;   // every K6 writer of a row stores its records
-    bc.rec_gidx = c->out_map();
+    bc.rec_gidx = A.map;
     bc.rec_base = idx_base;
     bc.handles = handles ? 1u : 0u;
     bc.htab = c->sub_tab.as<HandleSub>();
@@ -928,14 +1185,15 @@ static int batch_run_subs(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
     if (handles) bc.base = kHandleMark;   // whole-set fallback rows, marked for the pass after F4
     r = batch_slot_run(c, si, bc, s, ev);
     if (r) return r;
-    if (!out_rec && !handles && !global && idx_base) {   // (record form: K6 wrote the records)
-        DHT_TRY(launch_map_idx(out_idx, (uint64_t)q * k, nullptr, idx_base, s));
+    if (!out_rec && !handles && !global && (idx_base || A.view)) {   // (record form: K6 wrote the records)
+        // (a view's sub-partition maps give view indices: through its map to the set's)
+        DHT_TRY(launch_map_idx(out_idx, (uint64_t)q * k, A.view ? A.map : nullptr, idx_base, s));
     }
     return DHTGPU_OK;
 }
 
 // Batches of at most 64 targets: one pass over word 0 + one workgroup per target prefix (KS).
-static int small_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k, uint32_t* out_idx,
+static int small_run(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k, uint32_t* out_idx,
                      uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base, hipStream_t s, hipEvent_t* ev) {
     const int si = pick_slot(c, s);
     dhtgpu_ctx::BatchSlot& b = c->bslot[si];
@@ -951,7 +1209,7 @@ static int small_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q,
         b.spar = 0;
     }
     b.sclean = true;   // the kernels leave it zero
-    const uint32_t* gidx = c->out_map();
+    const uint32_t* gidx = A.map;
     uint32_t* li = out_idx;
     uint32_t* lc = out_cnt;
     if (out_rec) {
@@ -961,16 +1219,16 @@ static int small_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q,
         lc = b.out_cnt.as<uint32_t>();
     }
     BatchCall bc{};
-    bc.planes = c->planes.as<uint32_t>();
-    bc.stride = c->stride;
-    bc.n = c->n;
+    bc.planes = A.planes;
+    bc.stride = A.stride;
+    bc.n = A.n;
     bc.tp = tp;
     bc.ts = ts;
     bc.q = q;
     bc.q_plan = q;
     bc.k = k;
-    bc.skip = c->shard_pbits;
-    bc.w0s = c->shard_pbits ? c->w0s.as<uint32_t>() : nullptr;
+    bc.skip = A.pbits;
+    bc.w0s = A.w0s;
     bc.gidx = out_rec ? nullptr : gidx;
     bc.base = out_rec ? 0u : idx_base;
     bc.out_idx = li;
@@ -985,12 +1243,12 @@ static int small_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q,
     b.last = s;
     c->last_small = true;
     if (out_rec)
-        DHT_TRY(launch_rec3(li, (uint64_t)q * k, c->planes.as<uint32_t>(), c->stride, idx_base, gidx, out_rec, s));
+        DHT_TRY(launch_rec3(li, (uint64_t)q * k, A.planes, A.stride, idx_base, gidx, out_rec, s));
     return DHTGPU_OK;
 }
 
-static bool needs_subs(const dhtgpu_ctx* c, uint32_t q, uint32_t k) {
-    return c->n > (1ull << 24) && !batch_supported(c->n, q, k, c->num_cus) && q <= (1u << 22);
+static bool needs_subs(const dhtgpu_ctx* c, uint64_t n, uint32_t q, uint32_t k) {
+    return n > (1ull << 24) && !batch_supported(n, q, k, c->num_cus) && q <= (1u << 22);
 }
 
 static int batch_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k, uint32_t* out_idx,
@@ -1002,14 +1260,20 @@ static int batch_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q,
         ev = evs;
     }
     // DHTGPU_DBG bit 2^23: K6 for small batches too (comparison runs; the same exact results)
-    if (small_supported(c->n, q, k) && !(c->dbg & (1u << 23)))
-        return small_run(c, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s, ev);
+    dhtgpu_ctx::ActiveSet A;
+    if (int r = c->active_set(idx_base, &A)) return r;
+    if (A.view && !A.n) {   // every id rejected
+        c->last_small = true;   // (no statistics)
+        return answer_empty(q, k, out_idx, out_cnt, out_rec, s);
+    }
+    if (small_supported(A.n, q, k) && !(c->dbg & (1u << 23)))
+        return small_run(c, A, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s, ev);
     c->last_small = false;
-    if (needs_subs(c, q, k)) return batch_run_subs(c, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s, ev);
-    if (!batch_supported(c->n, q, k, c->num_cus)) return DHTGPU_ERANGE;
+    if (needs_subs(c, A.n, q, k)) return batch_run_subs(c, A, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s, ev);
+    if (!batch_supported(A.n, q, k, c->num_cus)) return DHTGPU_ERANGE;
     const int si = pick_slot(c, s);
     dhtgpu_ctx::BatchSlot& b = c->bslot[si];
-    const uint32_t* gidx = c->out_map();
+    const uint32_t* gidx = A.map;
     uint32_t* li = out_idx;
     uint32_t* lc = out_cnt;
     if (out_rec) {   // record form: the index rows are scratch (K6 stores the records themselves)
@@ -1019,17 +1283,17 @@ static int batch_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q,
         lc = b.out_cnt.as<uint32_t>();
     }
     BatchCall bc{};
-    bc.planes = c->planes.as<uint32_t>();
-    bc.stride = c->stride;
-    bc.n = c->n;
+    bc.planes = A.planes;
+    bc.stride = A.stride;
+    bc.n = A.n;
     bc.tp = tp;
     bc.ts = ts;
     bc.q = q;
     bc.q_plan = q;
     bc.k = k;
-    bc.skip = c->shard_pbits;
-    bc.pval = c->shard_pval;
-    bc.w0s = c->shard_pbits ? c->w0s.as<uint32_t>() : nullptr;
+    bc.skip = A.pbits;
+    bc.pval = A.pval;
+    bc.w0s = A.w0s;
     bc.gidx = out_rec ? nullptr : gidx;
     bc.base = out_rec ? 0u : idx_base;
     bc.out_idx = li;
@@ -1557,7 +1821,11 @@ int dhtgpu_net_prepare(dhtgpu_ctx* c, const uint8_t* dead, uint64_t table_seed) 
     if (!c) return DHTGPU_EINVAL;
     if (!c->has_ids || !c->n) return DHTGPU_ENOIDS;
     if (c->has_gidx) return DHTGPU_EINVAL;   // the network is the whole uploaded id set
-    int r = dhtgpu_index_build(c, c->stream);
+    DHT_TRY(c->bind());
+    // (the whole set's index whatever the accept mask says: the model has its own dead mask)
+    const dhtgpu_ctx::ActiveSet full{c->planes.as<uint32_t>(), c->stride, c->n, nullptr, nullptr, 0, 0, false,
+                                     &c->index, &c->index_B, &c->index_valid};
+    int r = index_build_on(full, c->stream, nullptr);
     if (r) return r;
     DHT_TRY(c->net_sorted.ensure((size_t)c->n * 8));
     DHT_TRY(launch_net_sort(c->index.p, c->n, c->index_B, c->net_sorted.as<uint2>(), c->stream));

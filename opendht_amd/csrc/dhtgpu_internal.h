@@ -51,6 +51,28 @@ hipError_t launch_select_prefix(const uint32_t* planes, uint64_t stride, uint64_
                                 hipStream_t s);
 uint64_t select_scratch_words(uint64_t n);
 
+// view.hip: the accept mask's live view.  A mask is stride / 32 words (id i = bit (i & 31) of
+// word i >> 5), zero past n, so that the kernels below read whole tiles of it unchecked.
+uint64_t view_mask_words(uint64_t stride);
+// bytes[32 * nwords] (device, 16-B aligned, nonzero = accepted) -> bits[nwords]
+hipError_t launch_view_pack(const uint8_t* bytes, uint64_t nwords, uint32_t* bits, hipStream_t s);
+// clears the bits past n in the word that holds bit n
+hipError_t launch_view_trim(uint32_t* bits, uint64_t n, hipStream_t s);
+// bit idx[j] = val[j] != 0, j < m (device arrays; idx < n checked by the caller)
+hipError_t launch_view_update(uint32_t* bits, const uint32_t* idx, const uint8_t* val, uint64_t m, hipStream_t s);
+// toff[stride / kTile] = exclusive offsets of the tiles' accepted ids, *d_total = their number
+hipError_t launch_view_count(const uint32_t* bits, uint64_t stride, uint32_t* toff, unsigned long long* d_total,
+                             hipStream_t s);
+// the accepted ids compacted in index order: out planes (out_stride), map[j] = set index of view id
+// j, w0s (nullable; shift in [1, 31]) = the view's shifted word-0 plane, gmap[j] = gidx[map[j]]
+// (both nullable).  Writes [0, total) of each only: the caller sizes them from *d_total and zeroes
+// the padding.
+hipError_t launch_view_compact(const uint32_t* planes, uint64_t stride, const uint32_t* bits, const uint32_t* toff,
+                               uint32_t* out, uint64_t out_stride, uint32_t* map, uint32_t* w0s, uint32_t shift,
+                               const uint32_t* gidx, uint32_t* gmap, hipStream_t s);
+// out[i] = map[i] + base, i < m
+hipError_t launch_view_add(const uint32_t* map, uint64_t m, uint32_t base, uint32_t* out, hipStream_t s);
+
 // scan.hip
 struct ScanPlan {
     uint32_t blocks_x;   // target groups

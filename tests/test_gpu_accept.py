@@ -1,0 +1,470 @@
+"""GPU parity of the accept mask (dhtgpu_set_accept ...): the flat k-NN paths -- K1, K4/K5, KS,
+K6 and its sub-partitions -- over the mask's live view, against the CPU oracle over the accepted
+ids mapped back to the original indices.  Marked gpu: run on the MI355X box."""
+import numpy as np
+import pytest
+
+import merge_util as MU
+import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+NONE = 0xFFFFFFFF
+EINVAL, EUNSORTED, ERANGE = -1, -5, -6
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import opendht_amd
+    c = opendht_amd.Context(0)
+    yield c
+    c.close()
+
+
+def expected(ids, mask, targets, k):
+    """The oracle over the accepted ids, mapped through sel to the original indices."""
+    sel = np.flatnonzero(mask)
+    q = targets.shape[0]
+    if sel.size == 0:
+        return np.full((q, k), NONE, np.uint32), np.zeros(q, np.uint32)
+    want, cnt = O.topk(ids[sel], targets, k, threads=16)
+    want = np.where(want == NONE, want, sel[np.minimum(want, sel.size - 1)].astype(np.uint32)).astype(np.uint32)
+    return want, cnt
+
+
+def assert_rows(got, cnt, want, wcnt, what):
+    assert np.array_equal(cnt, wcnt), what
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, f"{what}: {bad.size} rows differ, first {bad[:5]}: got {got[bad[0]]} want {want[bad[0]]}"
+
+
+# ---- 1. mask shapes x paths -----------------------------------------------------------------
+N1 = 3 * 4096 + 37   # a multiple of neither 32 nor the 4,096-id tile
+K1S = (1, 8, 32)
+Q1S = (3, 64, 150)   # K1's split merge / KS / K6
+
+
+def _masks():
+    rng = np.random.default_rng(11)
+    n = N1
+    m = {}
+    m["random"] = rng.random(n) < 0.5
+    m["all_ones"] = np.ones(n, bool)
+    m["all_zeros"] = np.zeros(n, bool)
+    m["first_only"] = np.arange(n) == 0
+    m["last_only"] = np.arange(n) == n - 1
+    km1 = np.zeros(n, bool)
+    km1[rng.choice(n, 7, replace=False)] = True   # k - 1 ids at k = 8 (fewer than k = 32, more than k = 1)
+    m["k_minus_1"] = km1
+    km31 = np.zeros(n, bool)
+    km31[rng.choice(n, 31, replace=False)] = True   # k - 1 ids at k = 32
+    m["k_minus_1_of_32"] = km31
+    m["alternating"] = (np.arange(n) & 1) == 1
+    eb = rng.random(n) < 0.5
+    eb[4096:8192] = False   # an empty tile ...
+    eb[8192:12288] = True   # ... and a full one
+    m["empty_and_full_tile"] = eb
+    m["last_37"] = np.arange(n) >= n - 37
+    return m
+
+
+@pytest.fixture(scope="module")
+def case1():
+    ids = O.gen_ids(7001, N1)
+    tgs = {q: O.gen_ids(7002 + q, q) for q in Q1S}
+    return ids, tgs, _masks()
+
+
+@pytest.mark.parametrize("name", ["random", "all_ones", "all_zeros", "first_only", "last_only", "k_minus_1", "k_minus_1_of_32",
+                                  "alternating", "empty_and_full_tile", "last_37"])
+def test_mask_shapes_all_paths(ctx, case1, name):
+    ids, tgs, masks = case1
+    mask = masks[name]
+    ctx.set_ids(ids)
+    ctx.set_accept(mask)
+    assert ctx.num_accepted == int(mask.sum())
+    for q in Q1S:
+        for k in K1S:
+            want, wcnt = expected(ids, mask, tgs[q], k)
+            for pname, fn in (("scan", ctx.topk), ("index", ctx.index_topk), ("batch", ctx.batch_topk)):
+                got, cnt = fn(tgs[q], k)
+                assert_rows(got, cnt, want, wcnt, f"{name} {pname} q={q} k={k}")
+    ctx.set_accept(None)
+
+
+# ---- 2. K6 proper ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def case2():
+    n, q = 1 << 20, 70000
+    ids = O.gen_ids(300 + q, n)
+    tg = O.gen_ids(301 + q, q)
+    mask = np.random.default_rng(12).random(n) < 0.5
+    return ids, tg, mask
+
+
+def test_k6_masked_vs_scan_and_oracle(ctx, case2):
+    ids, tg, mask = case2
+    q = tg.shape[0]
+    ctx.set_ids(ids)
+    ctx.set_accept(mask)
+    got, cnt = ctx.batch_topk(tg, 8)
+    sc, scnt = ctx.topk(tg, 8)
+    assert_rows(got, cnt, sc, scnt, "K6 vs masked K1")
+    rows = np.arange(0, q, q // 64)[:64]
+    want, wcnt = expected(ids, mask, tg[rows], 8)
+    assert_rows(got[rows], cnt[rows], want, wcnt, "K6 vs oracle")
+    ctx.set_accept(None)
+
+
+# ---- 3. device bitmask ----------------------------------------------------------------------
+def pack_bits(mask):
+    n = mask.shape[0]
+    pad = np.zeros((n + 31) // 32 * 32, np.uint8)
+    pad[:n] = mask
+    return np.packbits(pad.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32)
+
+
+def test_set_accept_bits_dev(ctx, case1):
+    import torch
+    ids, tgs, masks = case1
+    mask = masks["random"]
+    ctx.set_ids(ids)
+    ctx.set_accept(mask)
+    ref = [fn(tgs[150], 8) for fn in (ctx.topk, ctx.index_topk, ctx.batch_topk)]
+    ctx.set_accept(None)
+    words = pack_bits(mask)
+    words[-1] |= np.uint32(0xFFFFFFFF) << np.uint32(N1 & 31)   # bits past n are ignored
+    bits = torch.from_numpy(words.view(np.int32)).to("cuda:0")
+    torch.cuda.synchronize()
+    ctx.set_accept_bits_dev(bits.data_ptr())
+    assert ctx.num_accepted == int(mask.sum())
+    for (want, wcnt), fn in zip(ref, (ctx.topk, ctx.index_topk, ctx.batch_topk)):
+        got, cnt = fn(tgs[150], 8)
+        assert_rows(got, cnt, want, wcnt, "bits_dev")
+    ctx.set_accept(None)
+
+
+# ---- 4. update_accept -----------------------------------------------------------------------
+def test_update_accept(ctx, case1):
+    import opendht_amd
+    ids, _, _ = case1
+    k = 8
+    members = np.arange(5, N1, N1 // 40)[:40]
+    tg = ids[members]   # every target's nearest id is itself
+    ctx.set_ids(ids)
+    ctx.set_accept(np.ones(N1, bool))
+    full, fcnt = O.topk(ids, tg, k + 1)
+    assert np.array_equal(full[:, 0], members.astype(np.uint32))
+    for fn in (ctx.topk, ctx.index_topk, ctx.batch_topk):
+        got, cnt = fn(tg, k)
+        assert_rows(got, cnt, full[:, :k], np.minimum(fcnt, k), "all ones")
+    ctx.update_accept(members, 0)
+    assert ctx.num_accepted == N1 - members.size
+    for fn in (ctx.topk, ctx.index_topk, ctx.batch_topk):
+        got, cnt = fn(tg, k)
+        assert_rows(got, cnt, full[:, 1:], np.minimum(fcnt - 1, k), "nearest off: the former ranks 2..k+1")
+    with pytest.raises(opendht_amd.DhtGpuError) as e:
+        ctx.update_accept(np.array([members[1], N1], np.uint32), np.array([1, 1], np.uint8))
+    assert e.value.code == EINVAL
+    assert ctx.num_accepted == N1 - members.size   # nothing applied
+    got, cnt = ctx.batch_topk(tg, k)
+    assert_rows(got, cnt, full[:, 1:], np.minimum(fcnt - 1, k), "after the refused update")
+    ctx.update_accept(members, np.ones(members.size, np.uint8))
+    assert ctx.num_accepted == N1
+    for fn in (ctx.topk, ctx.index_topk, ctx.batch_topk):
+        got, cnt = fn(tg, k)
+        assert_rows(got, cnt, full[:, :k], np.minimum(fcnt, k), "on again")
+    ctx.set_accept(None)
+
+
+# ---- 5. lifecycle ---------------------------------------------------------------------------
+def test_lifecycle(ctx, case1):
+    ids, tgs, masks = case1
+    tg = tgs[150]
+    want, wcnt = O.topk(ids, tg, 8)
+    ctx.set_ids(ids)
+    ctx.set_accept(masks["random"])
+    got, cnt = ctx.batch_topk(tg, 8)
+    assert not np.array_equal(got, want)
+    ctx.set_accept(None)
+    assert ctx.num_accepted == N1
+    for fn in (ctx.topk, ctx.index_topk, ctx.batch_topk):
+        got, cnt = fn(tg, 8)
+        assert_rows(got, cnt, want, wcnt, "mask cleared")
+    ctx.set_accept(masks["alternating"])
+    assert ctx.num_accepted == int(masks["alternating"].sum())
+    ctx.set_ids(ids)   # a new id set clears the mask
+    assert ctx.num_accepted == N1
+    for fn in (ctx.topk, ctx.index_topk, ctx.batch_topk):
+        got, cnt = fn(tg, 8)
+        assert_rows(got, cnt, want, wcnt, "set_ids after a mask")
+    ctx.set_accept(np.ones(N1, np.uint8))
+    masked = [fn(tg, 8) for fn in (ctx.topk, ctx.index_topk, ctx.batch_topk)]
+    ctx.set_accept(None)
+    for (mg, mc), fn in zip(masked, (ctx.topk, ctx.index_topk, ctx.batch_topk)):
+        got, cnt = fn(tg, 8)
+        assert np.array_equal(got, mg) and np.array_equal(cnt, mc)
+        assert_rows(got, cnt, want, wcnt, "all ones == unmasked")
+
+
+# ---- 6. write_ids ---------------------------------------------------------------------------
+def test_write_ids(ctx, case1):
+    import opendht_amd
+    ids0, tgs, masks = case1
+    tg = tgs[150]
+    ids = ids0.copy()
+    ctx.set_ids(ids)
+    ctx.index_topk(tg, 8)   # an index and a K6 workspace exist
+    ctx.batch_topk(tg, 8)
+    rng = np.random.default_rng(13)
+    slots = np.sort(rng.choice(N1, 100, replace=False))
+    fresh = O.gen_ids(7100, 100)
+    fresh[:50] = tg[:50]   # half of them become some target's nearest id
+    for s, f in zip(slots, fresh):
+        ctx.write_ids(int(s), f.reshape(1, 20))
+    ids[slots] = fresh
+    assert np.array_equal(ctx.get_ids(), ids)
+    want, wcnt = O.topk(ids, tg, 8)
+    assert np.array_equal(want[:50, 0], slots[:50].astype(np.uint32))
+    for name, fn in (("scan", ctx.topk), ("index", ctx.index_topk), ("batch", ctx.batch_topk)):
+        got, cnt = fn(tg, 8)
+        assert_rows(got, cnt, want, wcnt, f"write_ids {name}")
+    # with a mask: overwritten slots that are masked off stay excluded until masked on
+    mask = masks["random"].copy()
+    mask[slots[:50]] = False
+    ctx.set_accept(mask)
+    ctx.index_topk(tg, 8)
+    ctx.batch_topk(tg, 8)
+    fresh2 = O.gen_ids(7101, 100)
+    fresh2[:50] = tg[50:100]
+    ctx.write_ids(int(slots[0]), fresh2[:1])
+    for s, f in zip(slots[1:], fresh2[1:]):
+        ctx.write_ids(int(s), f.reshape(1, 20))
+    ids[slots] = fresh2
+    want, wcnt = expected(ids, mask, tg, 8)
+    for name, fn in (("scan", ctx.topk), ("index", ctx.index_topk), ("batch", ctx.batch_topk)):
+        got, cnt = fn(tg, 8)
+        assert_rows(got, cnt, want, wcnt, f"masked write_ids {name}")
+    assert not np.isin(got, slots[:50]).any()
+    ctx.update_accept(slots[:50], 1)
+    mask[slots[:50]] = True
+    want, wcnt = expected(ids, mask, tg, 8)
+    assert np.array_equal(want[50:100, 0], slots[:50].astype(np.uint32))
+    for name, fn in (("scan", ctx.topk), ("index", ctx.index_topk), ("batch", ctx.batch_topk)):
+        got, cnt = fn(tg, 8)
+        assert_rows(got, cnt, want, wcnt, f"masked on {name}")
+    ctx.set_accept(None)
+    # a contiguous run, and the bounds
+    run = O.gen_ids(7102, 300)
+    ctx.write_ids(N1 - 300, run)
+    ids[N1 - 300:] = run
+    assert np.array_equal(ctx.get_ids(), ids)
+    with pytest.raises(opendht_amd.DhtGpuError) as e:
+        ctx.write_ids(N1 - 299, run)
+    assert e.value.code == ERANGE
+    # two equal ids: cached_nodes sees the recomputed sorted / unique state
+    ctx.cached_nodes(tg[:4], 8)
+    ctx.write_ids(17, ids[4000:4001])
+    with pytest.raises(opendht_amd.DhtGpuError) as e:
+        ctx.cached_nodes(tg[:4], 8)
+    assert e.value.code == EUNSORTED
+    with opendht_amd.Context(0) as shard:
+        shard.gen_ids_prefix(91, 20000, 3, 5)
+        with pytest.raises(opendht_amd.DhtGpuError) as e:
+            shard.write_ids(0, run[:1])
+        assert e.value.code == EINVAL
+
+
+# ---- 7. index forms -------------------------------------------------------------------------
+def _dev_targets(tg):
+    import torch
+    import opendht_amd
+    dev = torch.device("cuda", 0)
+    q = tg.shape[0]
+    ts = (q + 63) // 64 * 64
+    tp = torch.zeros(5 * ts, dtype=torch.int32, device=dev)
+    L = opendht_amd.lib()
+    assert L.dhtgpu_pack_dev(torch.from_numpy(tg.reshape(-1)).to(dev).data_ptr(), q, tp.data_ptr(), ts, None) == 0
+    torch.cuda.synchronize()
+    return tp, ts
+
+
+def test_idx_base_index_and_record_form(ctx, case1):
+    import torch
+    ids, tgs, masks = case1
+    mask = masks["random"]
+    words = ids.view(">u4").reshape(-1, 5).astype(np.uint32)
+    base, k = 1000, 8
+    ctx.set_ids(ids)
+    ctx.set_accept(mask)
+    dev = torch.device("cuda", 0)
+    for q in (3, 64, 150):   # K1 split merge / KS / K6
+        tg = tgs[q]
+        tp, ts = _dev_targets(tg)
+        want, wcnt = expected(ids, mask, tg, k)
+        wb = np.where(want == NONE, want, want + np.uint32(base)).astype(np.uint32)
+        wrec = np.full((q, k, 3), NONE, np.uint32)
+        ok = want != NONE
+        wrec[ok, 0] = words[want[ok].astype(np.int64), 0]
+        wrec[ok, 1] = words[want[ok].astype(np.int64), 1]
+        wrec[ok, 2] = wb[ok]
+        for name, fn in (("topk_dev", ctx.topk_dev), ("batch_topk_dev", ctx.batch_topk_dev),
+                         ("index_topk_dev", ctx.index_topk_dev)):
+            out = torch.full((q, k), -7, dtype=torch.int32, device=dev)
+            cnt = torch.full((q,), -7, dtype=torch.int32, device=dev)
+            fn(tp.data_ptr(), ts, q, k, out.data_ptr(), cnt.data_ptr(), None, base, ctx.stream)
+            torch.cuda.synchronize()
+            assert_rows(out.cpu().numpy().view(np.uint32), cnt.cpu().numpy().view(np.uint32), wb, wcnt,
+                        f"{name} q={q} index form")
+            rec = torch.full((q, k, 3), -7, dtype=torch.int32, device=dev)
+            fn(tp.data_ptr(), ts, q, k, None, None, rec.data_ptr(), base, ctx.stream)
+            torch.cuda.synchronize()
+            assert np.array_equal(rec.cpu().numpy().view(np.uint32), wrec), f"{name} q={q} record form"
+    ctx.set_accept(None)
+
+
+def test_masked_range_shards_merge():
+    """Two range-shard contexts with independent masks, record form -> dhtgpu_merge_dev + the tie
+    path as test_batch_records_merge drives it == the oracle over the concatenated masked set."""
+    import torch
+    import opendht_amd
+    n, q, k = 20000, 700, 8
+    ids = O.gen_ids(7201, 2 * n)
+    tg = O.gen_ids(7202, q)
+    rng = np.random.default_rng(14)
+    mask = rng.random(2 * n) < 0.5
+    tp, ts = _dev_targets(tg)
+    L = opendht_amd.lib()
+    dev = torch.device("cuda", 0)
+    bounds = [0, n, 2 * n]
+    rec = torch.empty((2, q, k, 3), dtype=torch.int32, device=dev)
+    shards = []
+    try:
+        for s in range(2):
+            c = opendht_amd.Context(0)
+            shards.append(c)
+            c.set_ids(ids[bounds[s]:bounds[s + 1]])
+            c.set_accept(mask[bounds[s]:bounds[s + 1]])
+            c.batch_topk_dev(tp.data_ptr(), ts, q, k, None, None, rec[s].data_ptr(), bounds[s], c.stream)
+            torch.cuda.synchronize()
+        out, cnt, nties = MU.merge(L, rec, tp, ts, k, ("ctx", MU.ctx_words_fn(L, shards, rec, bounds, k)))
+        want, wcnt = expected(ids, mask, tg, k)
+        assert nties == 0
+        assert_rows(out, cnt, want, wcnt, "merged masked shards")
+    finally:
+        for c in shards:
+            c.close()
+
+
+# ---- 8. prefix shard ------------------------------------------------------------------------
+def test_prefix_shard_masked():
+    import opendht_amd
+    n, pbits, pval, k = 200000, 3, 5, 8
+    ids = O.gen_ids(91, n)
+    top = ids[:, 0].astype(np.uint32) >> (8 - pbits)
+    gl = np.flatnonzero(top == pval).astype(np.uint32)   # shard-local -> stream index
+    shard = ids[gl]
+    mask = np.random.default_rng(15).random(shard.shape[0]) < 0.5
+    with opendht_amd.Context(0) as c:
+        c.gen_ids_prefix(91, n, pbits, pval)
+        assert c.num_ids == shard.shape[0]
+        c.set_accept(mask)   # indexed by shard-local position
+        assert c.num_accepted == int(mask.sum())
+        for q in (40, 5000):   # KS / K6
+            tg = O.gen_ids(7300 + q, q)
+            local, wcnt = expected(shard, mask, tg, k)
+            glob = np.where(local == NONE, local, gl[np.minimum(local, gl.size - 1)]).astype(np.uint32)
+            c.set_global_indices(True)
+            for name, fn in (("scan", c.topk), ("batch", c.batch_topk)):
+                got, cnt = fn(tg, k)
+                assert_rows(got, cnt, glob, wcnt, f"global {name} q={q}")
+            c.set_global_indices(False)
+            for name, fn in (("scan", c.topk), ("batch", c.batch_topk)):
+                got, cnt = fn(tg, k)
+                assert_rows(got, cnt, local, wcnt, f"local {name} q={q}")
+        # the K4 index answers the shard's own targets (as unmasked: test_prefix_shard_matches_global_topk)
+        tg = O.gen_ids(7399, 3000)
+        mine = tg[(tg[:, 0].astype(np.uint32) >> (8 - pbits)) == pval]
+        local, wcnt = expected(shard, mask, mine, k)
+        got, cnt = c.index_topk(mine, k)
+        assert_rows(got, cnt, local, wcnt, "local index")
+
+
+# ---- 9. sub-partitioned view ----------------------------------------------------------------
+def test_subpartitioned_view():
+    """3 * 2^24 ids, every third rejected: a view of 2^25 ids, 2^18 targets -- the shape of
+    test_subpartitions_k_sequence_fresh_context reached through the view.  At k = 8 one K6 plan
+    serves 2^25 ids on a 256-CU device; at k = 32 it cannot (batch_supported), so that is the call
+    that builds the two sub-partitions from the view: both are checked."""
+    import opendht_amd
+    n, q = 3 << 24, 1 << 18
+    mask = np.ones(n, np.uint8)
+    mask[::3] = 0
+    tg = O.gen_ids(7402, q)
+    rows = np.arange(0, q, q // 16)[:16]
+    c = opendht_amd.Context(0)
+    try:
+        c.gen_ids(7401, n)
+        c.set_accept(mask)
+        assert c.num_accepted == 1 << 25
+        c.set_sub_handles(1)
+        ids = O.gen_ids(7401, n)
+        sub = ids[np.flatnonzero(mask)]
+        del ids
+        first = {}
+        for k in (8, 32):
+            assert c.sub_handles_active(q, k) == 0
+            got, cnt = c.batch_topk(tg, k)
+            sc, scnt = c.topk(tg, k)
+            assert_rows(got, cnt, sc, scnt, f"view vs masked K1, k={k}")
+            w, wcnt = O.topk(sub, tg[rows], k, threads=16)
+            want = (w.astype(np.int64) + w.astype(np.int64) // 2 + 1).astype(np.uint32)   # j-th accepted id = j + j // 2 + 1
+            assert_rows(got[rows], cnt[rows], want, wcnt, f"view vs oracle, k={k}")
+            first[k] = got
+        del sub
+        off = int(first[8][rows[0], 0])   # one target's nearest id off: view and sub-partitions are rebuilt
+        c.update_accept(np.array([off], np.uint32), 0)
+        assert c.num_accepted == (1 << 25) - 1
+        for k in (32, 8):
+            got2, cnt2 = c.batch_topk(tg, k)
+            sc2, scnt2 = c.topk(tg, k)
+            assert_rows(got2, cnt2, sc2, scnt2, f"after update_accept, k={k}")
+            assert not (got2 == off).any() and (first[k] == off).any()
+            assert c.sub_handles_active(q, k) == 0
+    finally:
+        c.close()
+
+
+# ---- 10. streams ----------------------------------------------------------------------------
+def test_three_streams_share_the_view(ctx, case2):
+    import torch
+    ids, tg, mask = case2
+    q, k = tg.shape[0], 8
+    ctx.set_ids(ids)
+    ctx.set_accept(mask)
+    assert ctx.num_accepted == int(mask.sum())   # the view is built outside the loop
+    want, wcnt = ctx.batch_topk(tg, k)
+    tp, ts = _dev_targets(tg)
+    dev = torch.device("cuda", 0)
+    streams = [torch.cuda.Stream(dev) for _ in range(3)]
+    outs = [torch.full((q, k), -7, dtype=torch.int32, device=dev) for _ in range(3)]
+    cnts = [torch.full((q,), -7, dtype=torch.int32, device=dev) for _ in range(3)]
+    torch.cuda.synchronize()
+    for s, o, cn in zip(streams, outs, cnts):
+        ctx.batch_topk_dev(tp.data_ptr(), ts, q, k, o.data_ptr(), cn.data_ptr(), None, 0, s.cuda_stream)
+    torch.cuda.synchronize()
+    for o, cn in zip(outs, cnts):
+        assert_rows(o.cpu().numpy().view(np.uint32), cn.cpu().numpy().view(np.uint32), want, wcnt, "stream")
+    ctx.set_accept(None)
+
+
+# ---- the C++ adapter ------------------------------------------------------------------------
+def test_cpp_accept_adapter_on_gpu(tmp_path):
+    """ClosestIndex::set_accept_good + query against a host brute force with detail::xor_closer
+    (tests/cpp/accept_check.cpp --run: 5,000 nodes, 2,000 targets)."""
+    import subprocess
+    from test_accept_cpu import build_accept_check
+    exe = build_accept_check(str(tmp_path / "accept_check"))
+    out = subprocess.run([exe, "--run"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "0 mismatches" in out.stdout
