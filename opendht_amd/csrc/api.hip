@@ -1,6 +1,13 @@
-// api.hip -- the libdhtgpu C ABI (include/dhtgpu.h).  Owns device buffers and the
-// stream; converts between the boundary's 20-byte big-endian ids and the device
-// word-plane layout; never throws across the ABI.
+// api.hip -- the libdhtgpu C ABI (include/dhtgpu.h): the host side of every dhtgpu_* entry
+// point.  Converts between the boundary's 20-byte big-endian ids and the device word-plane
+// layout, checks arguments, sizes workspaces and issues the launch wrappers of
+// dhtgpu_internal.h; launches no kernel itself and never throws across the ABI.
+// Ownership: a DevBuf frees its device memory when it is destroyed, and the context's stream
+// and mapped hint are owners declared before every buffer, so deleting a dhtgpu_ctx releases
+// everything in order and an early return leaks nothing.
+// Layout: owners and the context; helpers shared by several entry points (each sequence stands
+// once); then the entry points by family -- id set, accept mask, K1, K4, K6, table, caches,
+// wire format, searches, crawl model.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
@@ -8,6 +15,7 @@
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/dhtgpu.h"
@@ -17,9 +25,20 @@ using namespace dhtgpu;
 
 namespace {
 
+// Device memory, owned: freed on destruction, move-only.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept {   // (what this held goes with o)
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
         if (p) (void)hipFree(p);
@@ -36,6 +55,48 @@ struct DevBuf {
     }
     template <class T>
     T* as() const { return static_cast<T*>(p); }
+};
+
+// The context's stream, owned (reads as the hipStream_t it holds).
+struct Stream {
+    hipStream_t h = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() {
+        if (h) (void)hipStreamDestroy(h);
+    }
+    operator hipStream_t() const { return h; }
+};
+
+// F4's fallback-list hint: mapped, coherent host memory (F4 stores it system-scope), owned.
+struct MappedHint {
+    uint32_t* host = nullptr;
+    uint32_t* dev = nullptr;   // its device address
+    MappedHint() = default;
+    MappedHint(const MappedHint&) = delete;
+    MappedHint& operator=(const MappedHint&) = delete;
+    ~MappedHint() {
+        if (host) (void)hipHostFree(host);
+    }
+};
+
+// N timing events, owned (created together; a creation that fails part-way leaks none).
+template <int N>
+struct Events {
+    hipEvent_t ev[N] = {};
+    Events() = default;
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+    ~Events() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create() {
+        for (hipEvent_t& e : ev)
+            if (hipError_t r = hipEventCreate(&e)) return r;
+        return hipSuccess;
+    }
 };
 
 int map_err(hipError_t e) {
@@ -62,12 +123,57 @@ bool verbose() {
 uint32_t pad_q(uint32_t q) { return (q + 63) & ~63u; }
 inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 
+// Lay N blocks of sz[i] bytes out in buf, each 256-byte aligned: p[i] = block i.
+template <size_t N>
+hipError_t carve(DevBuf& buf, const size_t (&sz)[N], uint8_t* (&p)[N]) {
+    size_t tot = 0;
+    for (size_t x : sz) tot += al256(x);
+    if (hipError_t e = buf.ensure(tot)) return e;
+    uint8_t* w = buf.as<uint8_t>();
+    for (size_t i = 0; i < N; ++i) {
+        p[i] = w;
+        w += al256(sz[i]);
+    }
+    return hipSuccess;
+}
+
+// Wire scratch behind `lead` bytes: n nodes' tails | q * nc candidates | q * 8 records | q lengths.
+size_t wire_bytes(size_t lead, uint64_t n, uint32_t alen, uint32_t q, uint32_t nc) {
+    return lead + al256((size_t)n * (alen + 2)) + al256((size_t)q * nc * 4) + al256((size_t)q * 8 * (20 + alen + 2)) +
+           al256((size_t)q * 4) + 256;
+}
+
+// one big-endian word of an id at the boundary
+inline uint32_t be32(const uint8_t* p) {
+    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+
+// nb bucket firsts (20-byte ids) as word planes: fp[w * nb + b]
+std::vector<uint32_t> firsts_planes(const uint8_t* firsts20, uint32_t nb) {
+    std::vector<uint32_t> fp((size_t)5 * nb);
+    for (uint32_t b = 0; b < nb; ++b)
+        for (int w = 0; w < 5; ++w) fp[(size_t)w * nb + b] = be32(firsts20 + 20 * (size_t)b + 4 * w);
+    return fp;
+}
+
+// Sub-partition split of n ids: the smallest s in [1, 8] with 2^s parts of <= 2^24 expected ids.
+uint32_t split_bits(uint64_t n) {
+    uint32_t sb = 1;
+    while (sb < 8 && (n >> sb) > (1ull << 24)) ++sb;
+    return sb;
+}
+
 }  // namespace
 
 struct dhtgpu_ctx {
     int device = 0;
     int num_cus = 256;
-    hipStream_t stream = nullptr;
+    // Members are destroyed in reverse order, after the destructor's body: every buffer below is
+    // freed first, then the mapped hint, the stream last.
+    Stream stream;
+    // fallback-list length of the context's last completed K6 call, written by F4 (a hint read
+    // without any sync: it sizes the next call's fallback-scan grid)
+    MappedHint fb_hint;
     DevBuf planes;          // 5 * stride u32
     uint64_t n = 0, stride = 0;
     bool sorted = false;
@@ -109,10 +215,6 @@ struct dhtgpu_ctx {
     };
     static constexpr int kBatchDepth = 4;
     BatchSlot bslot[kBatchDepth];
-    // fallback-list length of the context's last completed K6 call, written by F4 into mapped
-    // host memory (a hint read without any sync: it sizes the next call's fallback-scan grid)
-    uint32_t* fb_hint = nullptr;
-    uint32_t* fb_hint_dev = nullptr;
     int bnext = 0, blast = 0;
     bool last_small = false;   // the last K6-API call took the small-batch path
     uint64_t last_n = 0;       // ... else its plan: largest sub-partition, planned targets, sub-partitions
@@ -191,27 +293,38 @@ struct dhtgpu_ctx {
         DevBuf* index; uint32_t* index_B; bool* index_valid;   // the K4 index over these ids
     };
     int active_set(uint32_t idx_base, ActiveSet* out);   // brings the view up to date (may synchronise)
+    // the id set itself, whatever the accept mask says
+    ActiveSet full_set() {
+        return ActiveSet{planes.as<uint32_t>(), stride, n, out_map(), shard_pbits ? w0s.as<uint32_t>() : nullptr,
+                         shard_pbits, shard_pval, false, &index, &index_B, &index_valid};
+    }
     void clear_accept() {
         const bool was = acc.active;
-        acc.has_mask = acc.stale = acc.active = false;
-        acc.bmap_valid = acc.index_valid = false;
-        acc.n = 0;
-        for (DevBuf* b : {&acc.planes, &acc.map, &acc.w0s, &acc.gmap, &acc.bmap, &acc.index, &acc.toff, &acc.bits})
-            b->release();
+        acc = Accept{};
         if (was) invalidate_subs();   // they were built from the view
     }
 
     hipError_t bind() { return hipSetDevice(device); }
+    // the stream of a call: the caller's, else the context's
+    hipStream_t stream_or(void* s) const { return s ? (hipStream_t)s : stream.h; }
     void invalidate_subs() {
         subs_valid = false;
-        if (fb_hint) *fb_hint = 1u;   // a new set or split: the next call's list length is unknown
-        for (auto& sp : subs)
-            for (DevBuf* b : {&sp.planes, &sp.map, &sp.gmap, &sp.w0s}) b->release();
+        if (fb_hint.host) *fb_hint.host = 1u;   // a new set or split: the next call's list length is unknown
         subs.clear();
         sub_tab.release();
         cells.release();
         hinv.release();
         sub_bits = 0;
+    }
+
+    // Work in flight ends before anything is freed: the context's stream and every slot's last
+    // foreign stream.  The members then go as declared above (the caller has bound the device).
+    ~dhtgpu_ctx() {
+        if (stream.h) (void)hipStreamSynchronize(stream.h);
+        for (auto& b : bslot) {
+            if (b.last && b.last != stream.h) (void)hipStreamSynchronize(b.last);
+            if (b.done) (void)hipEventDestroy(b.done);
+        }
     }
 
     // upload q targets (20-byte big-endian, host) into target planes; returns stride
@@ -279,8 +392,7 @@ int dhtgpu_ctx::active_set(uint32_t idx_base, ActiveSet* out) {
     int r = ensure_view(this);
     if (r) return r;
     if (!acc.active) {
-        *out = ActiveSet{planes.as<uint32_t>(), stride, n, out_map(), shard_pbits ? w0s.as<uint32_t>() : nullptr,
-                         shard_pbits, shard_pval, false, &index, &index_B, &index_valid};
+        *out = full_set();
         return DHTGPU_OK;
     }
     const uint32_t* m = acc.map.as<uint32_t>();
@@ -307,6 +419,89 @@ static int answer_empty(uint32_t q, uint32_t k, uint32_t* out_idx, uint32_t* out
     if (out_idx) DHT_TRY(launch_fill(out_idx, (uint64_t)q * k, DHTGPU_NONE, s));
     if (out_cnt) DHT_TRY(launch_fill(out_cnt, q, 0u, s));
     if (out_rec) DHT_TRY(launch_fill(out_rec, (uint64_t)q * k * 3, DHTGPU_NONE, s));
+    return DHTGPU_OK;
+}
+
+// ---- sequences shared by several entry points -----------------------------------------------
+// n 20-byte ids (host) into the word planes at dst (stride), 2^22 ids (80 MB) of staging at a time.
+static int upload_ids(dhtgpu_ctx* c, const uint8_t* ids20, uint64_t n, uint32_t* dst, uint64_t stride) {
+    const uint64_t chunk = 1ull << 22;
+    DHT_TRY(c->staging.ensure((size_t)std::min<uint64_t>(n ? n : 1, chunk) * 20));
+    for (uint64_t i = 0; i < n; i += chunk) {
+        const uint64_t m = std::min(chunk, n - i);
+        DHT_TRY(hipMemcpyAsync(c->staging.p, ids20 + i * 20, (size_t)m * 20, hipMemcpyHostToDevice, c->stream));
+        DHT_TRY(launch_pack(c->staging.as<uint8_t>(), m, dst + i, stride, c->stream));
+        DHT_TRY(hipStreamSynchronize(c->stream));   // staging is reused
+    }
+    return DHTGPU_OK;
+}
+
+// The ids of a set that carry a prefix, in two passes over scratch carved from the context's aux:
+// count() (one host sync for the total, which sizes the caller's output), then compact().
+namespace {
+struct PrefixSelect {
+    const uint32_t* planes; uint64_t stride, n;
+    uint32_t pbits, pval;
+    hipStream_t s;
+    unsigned long long* d_total = nullptr;
+    uint32_t* scratch = nullptr;
+    int count(dhtgpu_ctx* c, unsigned long long* m) {
+        DHT_TRY(c->aux.ensure((size_t)select_scratch_words(n) * 4 + 16));
+        d_total = reinterpret_cast<unsigned long long*>(c->aux.as<uint8_t>());
+        scratch = reinterpret_cast<uint32_t*>(c->aux.as<uint8_t>() + 8);
+        DHT_TRY(launch_select_prefix(planes, stride, n, pbits, pval, scratch, d_total, nullptr, 0, nullptr, 0, s));
+        DHT_TRY(hipMemcpyAsync(m, d_total, 8, hipMemcpyDeviceToHost, s));
+        DHT_TRY(hipStreamSynchronize(s));
+        return DHTGPU_OK;
+    }
+    // out_idx (nullable): base + the set index of every selected id
+    hipError_t compact(uint32_t* out_planes, uint64_t out_stride, uint32_t* out_idx, uint64_t base) const {
+        return launch_select_prefix(planes, stride, n, pbits, pval, scratch, d_total, out_planes, out_stride, out_idx,
+                                    base, s);
+    }
+};
+}  // namespace
+
+// Where a call's local index rows go: the caller's rows, or -- record form, where the records are
+// made from the rows -- scratch rows of their own.
+static int local_rows(uint32_t* out_rec, DevBuf& idx, DevBuf& cnt, uint32_t q, uint32_t k, uint32_t** li, uint32_t** lc) {
+    if (!out_rec) return DHTGPU_OK;
+    DHT_TRY(idx.ensure((size_t)q * k * 4));
+    DHT_TRY(cnt.ensure((size_t)q * 4));
+    *li = idx.as<uint32_t>();
+    *lc = cnt.as<uint32_t>();
+    return DHTGPU_OK;
+}
+
+// The host form of a top-k call: upload the targets, run(target planes, stride, device rows,
+// device counts) on the context's stream, copy the rows back, synchronise.
+template <class Run>
+static int host_topk(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, uint32_t* out_idx, uint32_t* out_cnt,
+                     Run run) {
+    uint64_t ts = 0;
+    DHT_TRY(c->upload_targets(t20, q, &ts));
+    DHT_TRY(c->aux2.ensure((size_t)q * k * 4));
+    DHT_TRY(c->aux3.ensure((size_t)q * 4));
+    if (int r = run(c->targets.as<uint32_t>(), ts, c->aux2.as<uint32_t>(), c->aux3.as<uint32_t>())) return r;
+    DHT_TRY(hipMemcpyAsync(out_idx, c->aux2.p, (size_t)q * k * 4, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipMemcpyAsync(out_cnt, c->aux3.p, (size_t)q * 4, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    return DHTGPU_OK;
+}
+
+// Argument checks of the top-k calls: the _dev forms (index rows or records) and the host forms.
+static int check_topk_dev(const dhtgpu_ctx* c, const uint32_t* tp, uint32_t q, uint32_t k, const uint32_t* out_idx,
+                          const uint32_t* out_cnt, const uint32_t* out_rec) {
+    if (!c || k == 0 || k > DHTGPU_MAX_K || (q && !tp)) return DHTGPU_EINVAL;
+    if (!out_rec && (!out_idx || !out_cnt)) return DHTGPU_EINVAL;
+    if (!c->has_ids) return DHTGPU_ENOIDS;
+    return DHTGPU_OK;
+}
+
+static int check_topk_host(const dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, const uint32_t* out_idx,
+                           const uint32_t* out_cnt) {
+    if (!c || k == 0 || k > DHTGPU_MAX_K || (q && (!t20 || !out_idx || !out_cnt))) return DHTGPU_EINVAL;
+    if (!c->has_ids) return DHTGPU_ENOIDS;
     return DHTGPU_OK;
 }
 
@@ -342,7 +537,7 @@ int dhtgpu_ctx_create(int device, dhtgpu_ctx** out) {
     if (!c) return DHTGPU_ENOMEM;
     c->device = device;
     hipError_t e = c->bind();
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking);
     if (const char* d = getenv("DHTGPU_DBG")) c->dbg = (uint32_t)strtoul(d, nullptr, 0) & kDbgAllowed;
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
@@ -352,11 +547,11 @@ int dhtgpu_ctx_create(int device, dhtgpu_ctx** out) {
         void* h = nullptr;
         e = hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent);
         if (e == hipSuccess) {
-            c->fb_hint = static_cast<uint32_t*>(h);
-            *c->fb_hint = 1u;   // unknown: assume a fallback list (full-size grid)
+            c->fb_hint.host = static_cast<uint32_t*>(h);
+            *c->fb_hint.host = 1u;   // unknown: assume a fallback list (full-size grid)
             void* d = nullptr;
             e = hipHostGetDevicePointer(&d, h, 0);
-            c->fb_hint_dev = static_cast<uint32_t*>(d);
+            c->fb_hint.dev = static_cast<uint32_t*>(d);
         }
     }
     if (e != hipSuccess) {
@@ -370,28 +565,10 @@ int dhtgpu_ctx_create(int device, dhtgpu_ctx** out) {
 void dhtgpu_ctx_destroy(dhtgpu_ctx* c) {
     if (!c) return;
     (void)c->bind();
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& b : c->bslot) {   // slots last used on other streams: let that work finish
-        if (b.last && b.last != c->stream) (void)hipStreamSynchronize(b.last);
-        if (b.done) (void)hipEventDestroy(b.done);
-    }
-    for (DevBuf* b : {&c->planes, &c->staging, &c->targets, &c->out_idx, &c->out_cnt, &c->rec,
-                      &c->aux, &c->aux2, &c->aux3, &c->index, &c->gidx, &c->wire,
-                      &c->net_sorted, &c->net_dead, &c->net_io})
-        b->release();
-    for (auto& b : c->bslot)
-        for (DevBuf* d : {&b.ws, &b.out_idx, &b.out_cnt, &b.sws}) d->release();
-    c->clear_accept();
-    c->invalidate_subs();
-    if (c->fb_hint) (void)hipHostFree(c->fb_hint);
-    for (DevBuf* b : {&c->stamps, &c->w0s, &c->sview.planes, &c->sview.perm,
-                      &c->cache.planes, &c->cache.perm, &c->cache_in, &c->sort_scratch, &c->cache_acc, &c->srch})
-        b->release();
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
-void* dhtgpu_ctx_stream(dhtgpu_ctx* c) { return c ? (void*)c->stream : nullptr; }
+void* dhtgpu_ctx_stream(dhtgpu_ctx* c) { return c ? (void*)c->stream.h : nullptr; }
 
 uint64_t dhtgpu_num_ids(const dhtgpu_ctx* c) { return c && c->has_ids ? c->n : 0; }
 
@@ -433,14 +610,7 @@ int dhtgpu_set_ids(dhtgpu_ctx* c, const uint8_t* ids20, uint64_t n) {
     DHT_TRY(c->bind());
     int r = alloc_ids(c, n);
     if (r) return r;
-    const uint64_t chunk = 1ull << 22;   // 80 MB of staging at a time
-    DHT_TRY(c->staging.ensure((size_t)std::min<uint64_t>(n ? n : 1, chunk) * 20));
-    for (uint64_t i = 0; i < n; i += chunk) {
-        const uint64_t m = std::min(chunk, n - i);
-        DHT_TRY(hipMemcpyAsync(c->staging.p, ids20 + i * 20, (size_t)m * 20, hipMemcpyHostToDevice, c->stream));
-        DHT_TRY(launch_pack(c->staging.as<uint8_t>(), m, c->planes.as<uint32_t>() + i, c->stride, c->stream));
-        DHT_TRY(hipStreamSynchronize(c->stream));   // staging is reused
-    }
+    if ((r = upload_ids(c, ids20, n, c->planes.as<uint32_t>(), c->stride))) return r;
     return finish_ids(c, n);
 }
 
@@ -463,18 +633,13 @@ int dhtgpu_gen_ids_prefix(dhtgpu_ctx* c, uint64_t seed, uint64_t start, uint64_t
     DHT_TRY(c->staging.ensure((size_t)gs * 5 * 4));
     uint32_t* gen = c->staging.as<uint32_t>();
     DHT_TRY(launch_gen(seed, start, n, gen, gs, c->stream));
-    DHT_TRY(c->aux.ensure((size_t)select_scratch_words(n) * 4 + 16));
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(c->aux.as<uint8_t>());
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(c->aux.as<uint8_t>() + 8);
-    DHT_TRY(launch_select_prefix(gen, gs, n, pbits, pval, scratch, d_total, nullptr, 0, nullptr, 0, c->stream));
+    PrefixSelect sel{gen, gs, n, pbits, pval, c->stream};
     unsigned long long m = 0;
-    DHT_TRY(hipMemcpyAsync(&m, d_total, 8, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipStreamSynchronize(c->stream));
-    int r = alloc_ids(c, m);
+    int r = sel.count(c, &m);
     if (r) return r;
+    if ((r = alloc_ids(c, m))) return r;
     DHT_TRY(c->gidx.ensure((size_t)(m ? m : 1) * 4));
-    DHT_TRY(launch_select_prefix(gen, gs, n, pbits, pval, scratch, d_total, c->planes.as<uint32_t>(), c->stride,
-                                 c->gidx.as<uint32_t>(), start, c->stream));
+    DHT_TRY(sel.compact(c->planes.as<uint32_t>(), c->stride, c->gidx.as<uint32_t>(), start));
     r = finish_ids(c, m);
     if (r) return r;
     // the generation scratch (20 B per id of the whole stream) is not kept: a device may
@@ -555,7 +720,7 @@ int dhtgpu_set_accept_bits_dev(dhtgpu_ctx* c, const uint32_t* bits, void* stream
     if (!c || !bits) return DHTGPU_EINVAL;
     if (!c->has_ids) return DHTGPU_ENOIDS;
     DHT_TRY(c->bind());
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = c->stream_or(stream);
     int r = mask_alloc(c, s);
     if (r) return r;
     DHT_TRY(hipMemcpyAsync(c->acc.bits.p, bits, (size_t)((c->n + 31) / 32) * 4, hipMemcpyDeviceToDevice, s));
@@ -618,14 +783,7 @@ int dhtgpu_write_ids(dhtgpu_ctx* c, uint64_t first, const uint8_t* ids20, uint64
     c->net_valid = false;
     c->invalidate_subs();
     if (c->acc.has_mask) c->acc.stale = true;
-    const uint64_t chunk = 1ull << 22;
-    DHT_TRY(c->staging.ensure((size_t)std::min<uint64_t>(m, chunk) * 20));
-    for (uint64_t i = 0; i < m; i += chunk) {
-        const uint64_t mm = std::min(chunk, m - i);
-        DHT_TRY(hipMemcpyAsync(c->staging.p, ids20 + i * 20, (size_t)mm * 20, hipMemcpyHostToDevice, c->stream));
-        DHT_TRY(launch_pack(c->staging.as<uint8_t>(), mm, c->planes.as<uint32_t>() + first + i, c->stride, c->stream));
-        DHT_TRY(hipStreamSynchronize(c->stream));   // staging is reused
-    }
+    if (int r = upload_ids(c, ids20, m, c->planes.as<uint32_t>() + first, c->stride)) return r;
     return finish_ids(c, c->n);   // (padding untouched) the sorted / unique flag again
 }
 
@@ -643,7 +801,7 @@ int dhtgpu_handles_to_indices_dev(dhtgpu_ctx* c, const uint32_t* handles, uint64
     DHT_TRY(c->bind());
     const bool global = c->has_gidx && c->map_global;
     DHT_TRY(launch_handles_to_idx(c->sub_tab.as<HandleSub>(), (uint32_t)c->subs.size(), handles, m, out_idx, global,
-                                  global ? 0u : idx_base, stream ? (hipStream_t)stream : c->stream));
+                                  global ? 0u : idx_base, c->stream_or(stream)));
     return DHTGPU_OK;
 }
 
@@ -653,17 +811,12 @@ int dhtgpu_select_prefix_dev(dhtgpu_ctx* c, const uint32_t* planes, uint64_t str
     if (!c || !out_count || pbits > 16 || (pbits < 32 && pval >= (1u << pbits))) return DHTGPU_EINVAL;
     if (n && (!planes || !out_planes)) return DHTGPU_EINVAL;
     DHT_TRY(c->bind());
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    DHT_TRY(c->aux.ensure((size_t)select_scratch_words(n) * 4 + 16));
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(c->aux.as<uint8_t>());
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(c->aux.as<uint8_t>() + 8);
-    DHT_TRY(launch_select_prefix(planes, stride, n, pbits, pval, scratch, d_total, nullptr, 0, nullptr, 0, s));
+    hipStream_t s = c->stream_or(stream);
+    PrefixSelect sel{planes, stride, n, pbits, pval, s};
     unsigned long long m = 0;
-    DHT_TRY(hipMemcpyAsync(&m, d_total, 8, hipMemcpyDeviceToHost, s));
-    DHT_TRY(hipStreamSynchronize(s));
+    if (int r = sel.count(c, &m)) return r;
     if (m > out_stride) return DHTGPU_ERANGE;
-    DHT_TRY(launch_select_prefix(planes, stride, n, pbits, pval, scratch, d_total, out_planes, out_stride, out_gidx,
-                                 0, s));
+    DHT_TRY(sel.compact(out_planes, out_stride, out_gidx, 0));
     DHT_TRY(hipStreamSynchronize(s));
     *out_count = m;
     return DHTGPU_OK;
@@ -690,17 +843,9 @@ int dhtgpu_ids_dev(dhtgpu_ctx* c, const uint32_t** planes, uint64_t* stride) {
     return DHTGPU_OK;
 }
 
-int dhtgpu_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k,
-                    uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base,
-                    void* stream) {
-    if (!c || k == 0 || k > DHTGPU_MAX_K || (q && !tp)) return DHTGPU_EINVAL;
-    if (!out_rec && (!out_idx || !out_cnt)) return DHTGPU_EINVAL;
-    if (!c->has_ids) return DHTGPU_ENOIDS;
-    if (!q) return DHTGPU_OK;
-    DHT_TRY(c->bind());
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    dhtgpu_ctx::ActiveSet A;
-    if (int r = c->active_set(idx_base, &A)) return r;
+// K1 over an active set (checked arguments, q > 0)
+static int topk_on(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k,
+                   uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base, hipStream_t s) {
     if (A.view && !A.n) return answer_empty(q, k, out_idx, out_cnt, out_rec, s);
     const ScanPlan p = plan_scan(A.n, q, k, c->num_cus);
     const uint32_t* gidx = A.map;
@@ -711,14 +856,8 @@ int dhtgpu_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, 
     }
     // local indices (merged over id-range splits when the batch is too small to fill the
     // chip), then turned into candidate records or mapped to the final form
-    uint32_t* li = out_idx;
-    uint32_t* lc = out_cnt;
-    if (out_rec) {
-        DHT_TRY(c->out_idx.ensure((size_t)q * k * 4));
-        DHT_TRY(c->out_cnt.ensure((size_t)q * 4));
-        li = c->out_idx.as<uint32_t>();
-        lc = c->out_cnt.as<uint32_t>();
-    }
+    uint32_t *li = out_idx, *lc = out_cnt;
+    if (int r = local_rows(out_rec, c->out_idx, c->out_cnt, q, k, &li, &lc)) return r;
     if (one) {
         DHT_TRY(launch_scan(A.planes, A.stride, A.n, p, tp, ts, q, k, li, lc, nullptr, nullptr, 0, s));
     } else {
@@ -732,6 +871,17 @@ int dhtgpu_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, 
     else
         DHT_TRY(launch_map_idx(li, (uint64_t)q * k, gidx, idx_base, s));
     return DHTGPU_OK;
+}
+
+int dhtgpu_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k,
+                    uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base,
+                    void* stream) {
+    if (int r = check_topk_dev(c, tp, q, k, out_idx, out_cnt, out_rec)) return r;
+    if (!q) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    dhtgpu_ctx::ActiveSet A;
+    if (int r = c->active_set(idx_base, &A)) return r;
+    return topk_on(c, A, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, c->stream_or(stream));
 }
 
 int dhtgpu_merge_dev(const uint32_t* rec, uint32_t lists, uint32_t q, uint32_t k_in,
@@ -754,7 +904,7 @@ int dhtgpu_tie_words_dev(dhtgpu_ctx* c, const uint32_t* rec, uint32_t q, uint32_
     if (!c->has_ids) return DHTGPU_ENOIDS;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = c->stream_or(stream);
     // records name ids by global index: the prefix shard's ascending map, else idx_base + local
     const uint32_t* gmap = c->out_map();
     DHT_TRY(launch_tie_words(rec, q, k, ties, tie_cap, row_base, c->planes.as<uint32_t>(), c->stride, c->n, gmap,
@@ -792,21 +942,12 @@ int dhtgpu_gen_dev(uint64_t seed, uint64_t start, uint64_t n, uint32_t* planes, 
 
 int dhtgpu_topk(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, uint32_t* out_idx,
                 uint32_t* out_cnt) {
-    if (!c || k == 0 || k > DHTGPU_MAX_K || (q && (!t20 || !out_idx || !out_cnt))) return DHTGPU_EINVAL;
-    if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (int r = check_topk_host(c, t20, q, k, out_idx, out_cnt)) return r;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
-    uint64_t ts = 0;
-    DHT_TRY(c->upload_targets(t20, q, &ts));
-    DHT_TRY(c->aux2.ensure((size_t)q * k * 4));
-    DHT_TRY(c->aux3.ensure((size_t)q * 4));
-    int r = dhtgpu_topk_dev(c, c->targets.as<uint32_t>(), ts, q, k, c->aux2.as<uint32_t>(),
-                            c->aux3.as<uint32_t>(), nullptr, 0, c->stream);
-    if (r) return r;
-    DHT_TRY(hipMemcpyAsync(out_idx, c->aux2.p, (size_t)q * k * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipMemcpyAsync(out_cnt, c->aux3.p, (size_t)q * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipStreamSynchronize(c->stream));
-    return DHTGPU_OK;
+    return host_topk(c, t20, q, k, out_idx, out_cnt, [&](const uint32_t* tp, uint64_t ts, uint32_t* d_idx, uint32_t* d_cnt) {
+        return dhtgpu_topk_dev(c, tp, ts, q, k, d_idx, d_cnt, nullptr, 0, c->stream);
+    });
 }
 
 // the K4 index over an active set (the id set's own index, or the view's)
@@ -824,7 +965,7 @@ int dhtgpu_index_build(dhtgpu_ctx* c, void* stream) {
     if (!c) return DHTGPU_EINVAL;
     if (!c->has_ids) return DHTGPU_ENOIDS;
     DHT_TRY(c->bind());
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = c->stream_or(stream);
     dhtgpu_ctx::ActiveSet A;
     if (int r = c->active_set(0, &A)) return r;
     if (A.view && !A.n) return DHTGPU_OK;   // every id rejected: queries answer empty rows
@@ -835,30 +976,25 @@ int dhtgpu_index_build_timed(dhtgpu_ctx* c, void* stream, float* ms4) {
     if (!c || !ms4) return DHTGPU_EINVAL;
     if (!c->has_ids) return DHTGPU_ENOIDS;
     DHT_TRY(c->bind());
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = c->stream_or(stream);
     dhtgpu_ctx::ActiveSet A;
     if (int r = c->active_set(0, &A)) return r;
-    hipEvent_t ev[5];
-    for (int i = 0; i < 5; ++i) DHT_TRY(hipEventCreate(&ev[i]));
-    int r = index_build_on(A, s, ev);
-    hipError_t e = r ? hipSuccess : hipEventSynchronize(ev[4]);
-    for (int i = 0; !r && e == hipSuccess && i < 4; ++i) e = hipEventElapsedTime(&ms4[i], ev[i], ev[i + 1]);
-    for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]);
-    if (r) return r;
-    DHT_TRY(e);
+    Events<5> ev;
+    DHT_TRY(ev.create());
+    if (int r = index_build_on(A, s, ev.ev)) return r;
+    DHT_TRY(hipEventSynchronize(ev.ev[4]));
+    for (int i = 0; i < 4; ++i) DHT_TRY(hipEventElapsedTime(&ms4[i], ev.ev[i], ev.ev[i + 1]));
     return DHTGPU_OK;
 }
 
 int dhtgpu_index_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k,
                           uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base,
                           void* stream) {
-    if (!c || k == 0 || k > DHTGPU_MAX_K || (q && !tp)) return DHTGPU_EINVAL;
-    if (!out_rec && (!out_idx || !out_cnt)) return DHTGPU_EINVAL;
-    if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (int r = check_topk_dev(c, tp, q, k, out_idx, out_cnt, out_rec)) return r;
     if (!c->acc.has_mask && !c->index_valid) return DHTGPU_ENOIDS;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = c->stream_or(stream);
     dhtgpu_ctx::ActiveSet A;
     if (int r = c->active_set(idx_base, &A)) return r;
     if (A.view && !A.n) return answer_empty(q, k, out_idx, out_cnt, out_rec, s);
@@ -867,14 +1003,8 @@ int dhtgpu_index_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
         if (int r = index_build_on(A, s, nullptr)) return r;
     }
     const uint32_t* gidx = A.map;
-    uint32_t* li = out_idx;
-    uint32_t* lc = out_cnt;
-    if (out_rec) {   // candidate records for a cross-shard merge
-        DHT_TRY(c->out_idx.ensure((size_t)q * k * 4));
-        DHT_TRY(c->out_cnt.ensure((size_t)q * 4));
-        li = c->out_idx.as<uint32_t>();
-        lc = c->out_cnt.as<uint32_t>();
-    }
+    uint32_t *li = out_idx, *lc = out_cnt;   // (record form: candidate records for a cross-shard merge)
+    if (int r = local_rows(out_rec, c->out_idx, c->out_cnt, q, k, &li, &lc)) return r;
     DHT_TRY(launch_index_query(A.index->p, A.n, *A.index_B, A.planes, A.stride, tp, ts, q, k, li, lc, s));
     if (out_rec)
         DHT_TRY(launch_rec3(li, (uint64_t)q * k, A.planes, A.stride, idx_base, gidx, out_rec, s));
@@ -885,25 +1015,16 @@ int dhtgpu_index_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
 
 int dhtgpu_index_topk(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, uint32_t* out_idx,
                       uint32_t* out_cnt) {
-    if (!c || k == 0 || k > DHTGPU_MAX_K || (q && (!t20 || !out_idx || !out_cnt))) return DHTGPU_EINVAL;
-    if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (int r = check_topk_host(c, t20, q, k, out_idx, out_cnt)) return r;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
     if (!c->acc.has_mask && !c->index_valid) {   // (a view's index: built by the query below)
         int r = dhtgpu_index_build(c, c->stream);
         if (r) return r;
     }
-    uint64_t ts = 0;
-    DHT_TRY(c->upload_targets(t20, q, &ts));
-    DHT_TRY(c->aux2.ensure((size_t)q * k * 4));
-    DHT_TRY(c->aux3.ensure((size_t)q * 4));
-    int r = dhtgpu_index_topk_dev(c, c->targets.as<uint32_t>(), ts, q, k, c->aux2.as<uint32_t>(),
-                                  c->aux3.as<uint32_t>(), nullptr, 0, c->stream);
-    if (r) return r;
-    DHT_TRY(hipMemcpyAsync(out_idx, c->aux2.p, (size_t)q * k * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipMemcpyAsync(out_cnt, c->aux3.p, (size_t)q * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipStreamSynchronize(c->stream));
-    return DHTGPU_OK;
+    return host_topk(c, t20, q, k, out_idx, out_cnt, [&](const uint32_t* tp, uint64_t ts, uint32_t* d_idx, uint32_t* d_cnt) {
+        return dhtgpu_index_topk_dev(c, tp, ts, q, k, d_idx, d_cnt, nullptr, 0, c->stream);
+    });
 }
 
 // ---- K6 -------------------------------------------------------------------------------------
@@ -923,17 +1044,52 @@ static int pick_slot(dhtgpu_ctx* c, hipStream_t s) {
     return si;
 }
 
-// One K6 launch sequence on workspace slot `si` (stream s): waits for the slot's previous user
-// when that was another stream, cleans the workspace head when needed.
-static int batch_slot_run(dhtgpu_ctx* c, int si, BatchCall bc, hipStream_t s, hipEvent_t* ev) {
-    dhtgpu_ctx::BatchSlot& b = c->bslot[si];
-    // a slot last used on another stream: wait for that stream's work so far (it includes the
-    // slot's previous call); same stream: stream order suffices
+// A slot last used on another stream: s waits for that stream's work so far (it includes the
+// slot's previous call); same stream: stream order suffices.
+static int slot_wait(dhtgpu_ctx::BatchSlot& b, hipStream_t s) {
     if (b.last && b.last != s) {
         if (!b.done) DHT_TRY(hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
         DHT_TRY(hipEventRecord(b.done, b.last));
         DHT_TRY(hipStreamWaitEvent(s, b.done, 0));
     }
+    return DHTGPU_OK;
+}
+
+// The K6 / KS call over one active set: q targets at k, index rows li / lc, the result forms of
+// the public call (index form: A's map and idx_base; record form: K6 stores the records itself).
+// KS reads the set, target, row and event fields only.
+static BatchCall set_call(const dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32_t* tp, uint64_t ts, uint32_t q,
+                          uint32_t k, uint32_t* li, uint32_t* lc, uint32_t* out_rec, uint32_t idx_base, hipEvent_t* ev) {
+    BatchCall bc{};
+    bc.planes = A.planes;
+    bc.stride = A.stride;
+    bc.n = A.n;
+    bc.tp = tp;
+    bc.ts = ts;
+    bc.q = q;
+    bc.q_plan = q;
+    bc.k = k;
+    bc.skip = A.pbits;
+    bc.pval = A.pval;
+    bc.w0s = A.w0s;
+    bc.gidx = out_rec ? nullptr : A.map;
+    bc.base = out_rec ? 0u : idx_base;
+    bc.out_idx = li;
+    bc.out_cnt = lc;
+    bc.num_cus = c->num_cus;
+    bc.dbg = c->dbg;
+    bc.ev = ev;
+    bc.out_rec = out_rec;   // every K6 writer of a row stores its records
+    bc.rec_gidx = A.map;
+    bc.rec_base = idx_base;
+    return bc;
+}
+
+// One K6 launch sequence on workspace slot `si` (stream s): waits for the slot's previous user
+// when that was another stream, cleans the workspace head when needed.
+static int batch_slot_run(dhtgpu_ctx* c, int si, BatchCall bc, hipStream_t s, hipEvent_t* ev) {
+    dhtgpu_ctx::BatchSlot& b = c->bslot[si];
+    if (int r = slot_wait(b, s)) return r;
     uint64_t n_plan = bc.nsub ? 0 : bc.n;   // the plan is the largest sub-partition's
     for (uint32_t i = 0; i < bc.nsub; ++i) n_plan = std::max<uint64_t>(n_plan, bc.subs[i].n);
     const uint32_t nsub = bc.nsub ? bc.nsub : 1u;
@@ -946,8 +1102,8 @@ static int batch_slot_run(dhtgpu_ctx* c, int si, BatchCall bc, hipStream_t s, hi
         b.desc_sig = 0;
     }
     DHT_TRY(b.ws.ensure(need));
-    bc.fb_hint = c->fb_hint;
-    bc.fb_hint_dev = c->fb_hint_dev;
+    bc.fb_hint = c->fb_hint.host;
+    bc.fb_hint_dev = c->fb_hint.dev;
     // the head is zero after a call but for the statistics words ctr[0..3] (F1 resets them at the
     // start of the next call): a head laid out with its counters elsewhere (another bitmap size --
     // a sub-partitioned call, then a one-set call) would meet them inside another array (a partition
@@ -985,22 +1141,16 @@ static int batch_slot_run(dhtgpu_ctx* c, int si, BatchCall bc, hipStream_t s, hi
 static int build_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, bool sort) {
     if (c->subs_valid) return DHTGPU_OK;
     c->invalidate_subs();
-    uint32_t sb = 1;
-    while (sb < 8 && (A.n >> sb) > (1ull << 24)) ++sb;
+    const uint32_t sb = split_bits(A.n);
     const uint32_t P = A.pbits + sb;   // prefix bits every id of a sub-partition shares
     if (P > 24) return DHTGPU_ERANGE;
     hipStream_t s = c->stream;
-    DHT_TRY(c->aux.ensure((size_t)select_scratch_words(A.n) * 4 + 16));
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(c->aux.as<uint8_t>());
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(c->aux.as<uint8_t>() + 8);
-    const uint32_t* planes = A.planes;   // (a view: "context-local" below is the view's index)
     c->subs.resize((size_t)1 << sb);
     for (uint32_t i = 0; i < (1u << sb); ++i) {
-        const uint32_t pv = (A.pval << sb) | i;
-        DHT_TRY(launch_select_prefix(planes, A.stride, A.n, P, pv, scratch, d_total, nullptr, 0, nullptr, 0, s));
+        // (a view: "context-local" below is the view's index)
+        PrefixSelect sel{A.planes, A.stride, A.n, P, (A.pval << sb) | i, s};
         unsigned long long m = 0;
-        DHT_TRY(hipMemcpyAsync(&m, d_total, 8, hipMemcpyDeviceToHost, s));
-        DHT_TRY(hipStreamSynchronize(s));
+        if (int r = sel.count(c, &m)) return r;
         dhtgpu_ctx::SubPart& sp = c->subs[i];
         sp.n = m;
         sp.stride = pad_ids(m ? m : 1);
@@ -1009,27 +1159,21 @@ static int build_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, bool sort) 
         DHT_TRY(sp.w0s.ensure((size_t)sp.stride * 4));
         for (int w = 0; w < 5; ++w)   // deterministic padding words (F2 may read them, masked)
             DHT_TRY(launch_fill(sp.planes.as<uint32_t>() + (uint64_t)w * sp.stride + m, sp.stride - m, 0u, s));
-        DHT_TRY(launch_select_prefix(planes, A.stride, A.n, P, pv, scratch, d_total, sp.planes.as<uint32_t>(),
-                                     sp.stride, sp.map.as<uint32_t>(), 0, s));
+        DHT_TRY(sel.compact(sp.planes.as<uint32_t>(), sp.stride, sp.map.as<uint32_t>(), 0));
         if (sort && m > 1) {   // prefix order (stable sort of the compacted ids; perm -> context-local map)
             DevBuf sorted, perm, sscr;
             int unique = 1;
-            hipError_t e = sorted.ensure((size_t)sp.stride * 5 * 4);
-            if (e == hipSuccess) e = perm.ensure((size_t)m * 4);
-            if (e == hipSuccess) e = sscr.ensure(sort_scratch_bytes(m));
-            for (int w = 0; e == hipSuccess && w < 5; ++w)
-                e = launch_fill(sorted.as<uint32_t>() + (uint64_t)w * sp.stride + m, sp.stride - m, 0u, s);
-            if (e == hipSuccess)
-                e = launch_sort_ids(sp.planes.as<uint32_t>(), sp.stride, m, sorted.as<uint32_t>(), sp.stride,
-                                    perm.as<uint32_t>(), sscr.p, &unique, s);
-            if (e == hipSuccess) e = launch_map_idx(perm.as<uint32_t>(), m, sp.map.as<uint32_t>(), 0, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(sp.map.p, perm.p, (size_t)m * 4, hipMemcpyDeviceToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e == hipSuccess) std::swap(sp.planes, sorted);
-            sorted.release();
-            perm.release();
-            sscr.release();
-            DHT_TRY(e);
+            DHT_TRY(sorted.ensure((size_t)sp.stride * 5 * 4));
+            DHT_TRY(perm.ensure((size_t)m * 4));
+            DHT_TRY(sscr.ensure(sort_scratch_bytes(m)));
+            for (int w = 0; w < 5; ++w)
+                DHT_TRY(launch_fill(sorted.as<uint32_t>() + (uint64_t)w * sp.stride + m, sp.stride - m, 0u, s));
+            DHT_TRY(launch_sort_ids(sp.planes.as<uint32_t>(), sp.stride, m, sorted.as<uint32_t>(), sp.stride,
+                                    perm.as<uint32_t>(), sscr.p, &unique, s));
+            DHT_TRY(launch_map_idx(perm.as<uint32_t>(), m, sp.map.as<uint32_t>(), 0, s));
+            DHT_TRY(hipMemcpyAsync(sp.map.p, perm.p, (size_t)m * 4, hipMemcpyDeviceToDevice, s));
+            DHT_TRY(hipStreamSynchronize(s));
+            std::swap(sp.planes, sorted);
         }
         DHT_TRY(launch_shift_w0(sp.planes.as<uint32_t>(), sp.stride, P, sp.w0s.as<uint32_t>(), s));
         if (c->has_gidx) {   // sub -> global stream index, composed once
@@ -1042,19 +1186,17 @@ static int build_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, bool sort) 
     const size_t ncell = (size_t)1 << cell_level();
     DHT_TRY(c->cells.ensure(c->subs.size() * ncell));
     {
-        DevBuf cnt;   // (DevBuf frees nothing by itself: released on every path)
-        hipError_t e = cnt.ensure(ncell * 4);
-        for (size_t i = 0; e == hipSuccess && i < c->subs.size(); ++i)
-            e = launch_cell_counts(c->subs[i].w0s.as<uint32_t>(), c->subs[i].n, cnt.as<uint32_t>(),
-                                   c->cells.as<uint8_t>() + i * ncell, s);
-        for (size_t i = 0; sort && e == hipSuccess && i < c->subs.size(); ++i) {   // window bounds (sorted subs)
-            e = launch_cell_spans(c->subs[i].w0s.as<uint32_t>(), c->subs[i].n, cnt.as<uint32_t>(), s);
-            if (e == hipSuccess) e = hipMemcpyAsync(c->subs[i].span, cnt.p, 32 * 4, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
+        DevBuf cnt;
+        DHT_TRY(cnt.ensure(ncell * 4));
+        for (size_t i = 0; i < c->subs.size(); ++i)
+            DHT_TRY(launch_cell_counts(c->subs[i].w0s.as<uint32_t>(), c->subs[i].n, cnt.as<uint32_t>(),
+                                       c->cells.as<uint8_t>() + i * ncell, s));
+        for (size_t i = 0; sort && i < c->subs.size(); ++i) {   // window bounds (sorted subs)
+            DHT_TRY(launch_cell_spans(c->subs[i].w0s.as<uint32_t>(), c->subs[i].n, cnt.as<uint32_t>(), s));
+            DHT_TRY(hipMemcpyAsync(c->subs[i].span, cnt.p, 32 * 4, hipMemcpyDeviceToHost, s));
+            DHT_TRY(hipStreamSynchronize(s));
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        cnt.release();
-        DHT_TRY(e);
+        DHT_TRY(hipStreamSynchronize(s));
         c->spans.assign(sort ? c->subs.size() * 32 : 0, 0u);
         for (size_t i = 0; sort && i < c->subs.size(); ++i)
             std::copy(c->subs[i].span, c->subs[i].span + 32, c->spans.begin() + i * 32);
@@ -1101,8 +1243,7 @@ static int batch_run_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const u
     // builds them.
     bool sort = false;
     {
-        uint32_t sbe = 1;
-        while (sbe < 8 && (A.n >> sbe) > (1ull << 24)) ++sbe;
+        const uint32_t sbe = split_bits(A.n);   // (the split build_subs makes)
         const uint64_t nsub_e = A.n >> sbe;
         const double qsub = (double)q / (double)(1u << sbe);
         uint32_t lm = 0;
@@ -1120,28 +1261,20 @@ static int batch_run_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const u
     for (const auto& sp : c->subs) n_max = std::max<uint64_t>(n_max, sp.n);
     const bool handles = c->sub_handles && !out_rec && !c->acc.has_mask;   // (masked calls return indices)
     if (!batch_supported(n_max, q_plan, k, c->num_cus, S, pf)) {
-        if (!handles) return dhtgpu_topk_dev(c, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s);
-        // handles on the K1 route: context-local indices, then their handles
-        const bool mg = c->map_global;
-        c->map_global = false;
-        r = dhtgpu_topk_dev(c, tp, ts, q, k, out_idx, out_cnt, nullptr, 0, s);
-        c->map_global = mg;
-        if (r) return r;
+        if (!handles) return topk_on(c, A, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s);
+        // handles on the K1 route: context-local indices (handles go with no mask, so A is the set
+        // itself; its global map and the offset are left out), then their handles
+        dhtgpu_ctx::ActiveSet L = A;
+        L.map = nullptr;
+        if ((r = topk_on(c, L, tp, ts, q, k, out_idx, out_cnt, nullptr, 0, s))) return r;
         DHT_TRY(launch_idx_to_handles(c->hinv.as<uint32_t>(), out_idx, (uint64_t)q * k, s));
         return DHTGPU_OK;
     }
     const bool global = !handles && c->has_gidx && c->map_global && !out_rec;
     const int si = pick_slot(c, s);
     dhtgpu_ctx::BatchSlot& b = c->bslot[si];
-    // record form: the index rows are scratch (K6 stores the records themselves)
-    uint32_t* li = out_idx;
-    uint32_t* lc = out_cnt;
-    if (out_rec) {
-        DHT_TRY(b.out_idx.ensure((size_t)q * k * 4));
-        DHT_TRY(b.out_cnt.ensure((size_t)q * 4));
-        li = b.out_idx.as<uint32_t>();
-        lc = b.out_cnt.as<uint32_t>();
-    }
+    uint32_t *li = out_idx, *lc = out_cnt;
+    if ((r = local_rows(out_rec, b.out_idx, b.out_cnt, q, k, &li, &lc))) return r;
     std::vector<SubSpec> specs(S);
     uint64_t off = 0;
     for (uint32_t i = 0; i < S; ++i) {
@@ -1151,38 +1284,23 @@ static int batch_run_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const u
                            handles ? (uint32_t)off : 0u};
         off += sp.n;
     }
-    BatchCall bc{};
-    bc.planes = A.planes;   // F4's scan: the whole set
-    bc.stride = A.stride;
-    bc.n = A.n;
-    bc.tp = tp;
-    bc.ts = ts;
-    bc.q = q;
+    // the whole set is F4's scan; the sub-partitions carry their own shifted planes and maps
+    BatchCall bc = set_call(c, A, tp, ts, q, k, li, lc, out_rec, idx_base, ev);
     bc.q_plan = q_plan;
-    bc.k = k;
     bc.skip = P;
-    bc.pval = A.pval;
+    bc.w0s = nullptr;
     bc.cells = c->cells.as<uint8_t>();
     bc.spans = c->spans.empty() ? nullptr : c->spans.data();
     bc.sorted = c->subs_sorted ? 1u : 0u;
-    bc.gidx = global ? A.map : nullptr;
-    bc.base = 0;
-    bc.out_idx = li;
-    bc.out_cnt = lc;
-    bc.num_cus = c->num_cus;
-    bc.dbg = c->dbg;
-    bc.ev = ev;
+    bc.gidx = global ? A.map : nullptr;   // (else mapped after the call, below)
+    bc.base = handles ? kHandleMark : 0u;   // handles: whole-set fallback rows, marked for the pass after F4
     bc.subs = specs.data();
     bc.nsub = S;
     bc.sub_shift = A.pbits;
     bc.sub_bits = sb;
-    bc.out_rec = out_rec;   // every K6 writer of a row stores its records
-    bc.rec_gidx = A.map;
-    bc.rec_base = idx_base;
     bc.handles = handles ? 1u : 0u;
     bc.htab = c->sub_tab.as<HandleSub>();
     bc.hinv = c->hinv.as<uint32_t>();
-    if (handles) bc.base = kHandleMark;   // whole-set fallback rows, marked for the pass after F4
     r = batch_slot_run(c, si, bc, s, ev);
     if (r) return r;
     if (!out_rec && !handles && !global && (idx_base || A.view)) {   // (record form: K6 wrote the records)
@@ -1197,11 +1315,7 @@ static int small_run(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32
                      uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base, hipStream_t s, hipEvent_t* ev) {
     const int si = pick_slot(c, s);
     dhtgpu_ctx::BatchSlot& b = c->bslot[si];
-    if (b.last && b.last != s) {   // the slot's previous user on another stream
-        if (!b.done) DHT_TRY(hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
-        DHT_TRY(hipEventRecord(b.done, b.last));
-        DHT_TRY(hipStreamWaitEvent(s, b.done, 0));
-    }
+    if (int r = slot_wait(b, s)) return r;
     if (b.sws.cap < small_bytes()) b.sclean = false;
     DHT_TRY(b.sws.ensure(small_bytes()));
     if (!b.sclean) {
@@ -1209,32 +1323,9 @@ static int small_run(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32
         b.spar = 0;
     }
     b.sclean = true;   // the kernels leave it zero
-    const uint32_t* gidx = A.map;
-    uint32_t* li = out_idx;
-    uint32_t* lc = out_cnt;
-    if (out_rec) {
-        DHT_TRY(b.out_idx.ensure((size_t)q * k * 4));
-        DHT_TRY(b.out_cnt.ensure((size_t)q * 4));
-        li = b.out_idx.as<uint32_t>();
-        lc = b.out_cnt.as<uint32_t>();
-    }
-    BatchCall bc{};
-    bc.planes = A.planes;
-    bc.stride = A.stride;
-    bc.n = A.n;
-    bc.tp = tp;
-    bc.ts = ts;
-    bc.q = q;
-    bc.q_plan = q;
-    bc.k = k;
-    bc.skip = A.pbits;
-    bc.w0s = A.w0s;
-    bc.gidx = out_rec ? nullptr : gidx;
-    bc.base = out_rec ? 0u : idx_base;
-    bc.out_idx = li;
-    bc.out_cnt = lc;
-    bc.num_cus = c->num_cus;
-    bc.ev = ev;
+    uint32_t *li = out_idx, *lc = out_cnt;
+    if (int r = local_rows(out_rec, b.out_idx, b.out_cnt, q, k, &li, &lc)) return r;
+    const BatchCall bc = set_call(c, A, tp, ts, q, k, li, lc, out_rec, idx_base, ev);
     if (hipError_t e = launch_small_topk(bc, b.sws.p, b.spar, s)) {
         b.sclean = false;   // S1 may have counted into this call's set: the next call re-zeroes it all
         return map_err(e);
@@ -1242,8 +1333,8 @@ static int small_run(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32
     b.spar ^= 1u;
     b.last = s;
     c->last_small = true;
-    if (out_rec)
-        DHT_TRY(launch_rec3(li, (uint64_t)q * k, A.planes, A.stride, idx_base, gidx, out_rec, s));
+    if (out_rec)   // (KS stores index rows only: the records are made from them)
+        DHT_TRY(launch_rec3(li, (uint64_t)q * k, A.planes, A.stride, idx_base, A.map, out_rec, s));
     return DHTGPU_OK;
 }
 
@@ -1273,50 +1364,19 @@ static int batch_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q,
     if (!batch_supported(A.n, q, k, c->num_cus)) return DHTGPU_ERANGE;
     const int si = pick_slot(c, s);
     dhtgpu_ctx::BatchSlot& b = c->bslot[si];
-    const uint32_t* gidx = A.map;
-    uint32_t* li = out_idx;
-    uint32_t* lc = out_cnt;
-    if (out_rec) {   // record form: the index rows are scratch (K6 stores the records themselves)
-        DHT_TRY(b.out_idx.ensure((size_t)q * k * 4));
-        DHT_TRY(b.out_cnt.ensure((size_t)q * 4));
-        li = b.out_idx.as<uint32_t>();
-        lc = b.out_cnt.as<uint32_t>();
-    }
-    BatchCall bc{};
-    bc.planes = A.planes;
-    bc.stride = A.stride;
-    bc.n = A.n;
-    bc.tp = tp;
-    bc.ts = ts;
-    bc.q = q;
-    bc.q_plan = q;
-    bc.k = k;
-    bc.skip = A.pbits;
-    bc.pval = A.pval;
-    bc.w0s = A.w0s;
-    bc.gidx = out_rec ? nullptr : gidx;
-    bc.base = out_rec ? 0u : idx_base;
-    bc.out_idx = li;
-    bc.out_cnt = lc;
-    bc.num_cus = c->num_cus;
-    bc.dbg = c->dbg;
-    bc.ev = ev;
-    bc.out_rec = out_rec;   // every K6 writer of a row stores its records
-    bc.rec_gidx = gidx;
-    bc.rec_base = idx_base;
-    return batch_slot_run(c, si, bc, s, ev);   // (record form: K6 writes the records itself)
+    uint32_t *li = out_idx, *lc = out_cnt;
+    if (int r = local_rows(out_rec, b.out_idx, b.out_cnt, q, k, &li, &lc)) return r;
+    return batch_slot_run(c, si, set_call(c, A, tp, ts, q, k, li, lc, out_rec, idx_base, ev), s, ev);
 }
 
 int dhtgpu_batch_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k,
                           uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base,
                           void* stream) {
-    if (!c || k == 0 || k > DHTGPU_MAX_K || (q && !tp)) return DHTGPU_EINVAL;
-    if (!out_rec && (!out_idx || !out_cnt)) return DHTGPU_EINVAL;
-    if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (int r = check_topk_dev(c, tp, q, k, out_idx, out_cnt, out_rec)) return r;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
     return batch_run(c, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base,
-                     stream ? (hipStream_t)stream : c->stream, nullptr);
+                     c->stream_or(stream), nullptr);
 }
 
 int dhtgpu_batch_events(dhtgpu_ctx* c, void** ev8) {
@@ -1334,16 +1394,13 @@ int dhtgpu_batch_topk_timed(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint
     if (!c || !ms4 || k == 0 || k > DHTGPU_MAX_K || !q || !tp || !out_idx || !out_cnt) return DHTGPU_EINVAL;
     if (!c->has_ids) return DHTGPU_ENOIDS;
     DHT_TRY(c->bind());
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    hipEvent_t ev[8];   // start/stop per kernel, recorded by the kernels' own dispatches
-    for (int i = 0; i < 8; ++i) DHT_TRY(hipEventCreate(&ev[i]));
-    int r = batch_run(c, tp, ts, q, k, out_idx, out_cnt, nullptr, 0, s, ev);
-    hipError_t e = r ? hipSuccess : hipStreamSynchronize(s);
-    if (!r && e == hipSuccess) e = hipEventSynchronize(ev[7]);
-    for (int i = 0; !r && e == hipSuccess && i < 4; ++i) e = hipEventElapsedTime(&ms4[i], ev[2 * i], ev[2 * i + 1]);
-    for (int i = 0; i < 8; ++i) (void)hipEventDestroy(ev[i]);
-    if (r) return r;
-    DHT_TRY(e);
+    hipStream_t s = c->stream_or(stream);
+    Events<8> ev;   // start/stop per kernel, recorded by the kernels' own dispatches
+    DHT_TRY(ev.create());
+    if (int r = batch_run(c, tp, ts, q, k, out_idx, out_cnt, nullptr, 0, s, ev.ev)) return r;
+    DHT_TRY(hipStreamSynchronize(s));
+    DHT_TRY(hipEventSynchronize(ev.ev[7]));
+    for (int i = 0; i < 4; ++i) DHT_TRY(hipEventElapsedTime(&ms4[i], ev.ev[2 * i], ev.ev[2 * i + 1]));
     if (stats4 && c->last_small) {   // the small-batch path keeps no statistics
         for (int i = 0; i < 4; ++i) stats4[i] = 0;
     } else if (stats4) {
@@ -1355,21 +1412,12 @@ int dhtgpu_batch_topk_timed(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint
 
 int dhtgpu_batch_topk(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, uint32_t* out_idx,
                       uint32_t* out_cnt) {
-    if (!c || k == 0 || k > DHTGPU_MAX_K || (q && (!t20 || !out_idx || !out_cnt))) return DHTGPU_EINVAL;
-    if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (int r = check_topk_host(c, t20, q, k, out_idx, out_cnt)) return r;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
-    uint64_t ts = 0;
-    DHT_TRY(c->upload_targets(t20, q, &ts));
-    DHT_TRY(c->aux2.ensure((size_t)q * k * 4));
-    DHT_TRY(c->aux3.ensure((size_t)q * 4));
-    int r = batch_run(c, c->targets.as<uint32_t>(), ts, q, k, c->aux2.as<uint32_t>(), c->aux3.as<uint32_t>(),
-                      nullptr, 0, c->stream, nullptr);
-    if (r) return r;
-    DHT_TRY(hipMemcpyAsync(out_idx, c->aux2.p, (size_t)q * k * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipMemcpyAsync(out_cnt, c->aux3.p, (size_t)q * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipStreamSynchronize(c->stream));
-    return DHTGPU_OK;
+    return host_topk(c, t20, q, k, out_idx, out_cnt, [&](const uint32_t* tp, uint64_t ts, uint32_t* d_idx, uint32_t* d_cnt) {
+        return batch_run(c, tp, ts, q, k, d_idx, d_cnt, nullptr, 0, c->stream, nullptr);
+    });
 }
 
 int dhtgpu_find_closest(dhtgpu_ctx* c, uint32_t nb, const uint8_t* firsts20, const uint32_t* off,
@@ -1393,12 +1441,9 @@ int dhtgpu_find_closest(dhtgpu_ctx* c, uint32_t nb, const uint8_t* firsts20, con
     DHT_TRY(c->bind());
     // host snapshot -> one device blob: firsts planes | off | gcnt | node planes | good
     const uint64_t ns = pad_q(nn ? nn : 1);
-    std::vector<uint32_t> fp((size_t)5 * nb), gcnt(nb);
+    const std::vector<uint32_t> fp = firsts_planes(firsts20, nb);
+    std::vector<uint32_t> gcnt(nb);
     for (uint32_t b = 0; b < nb; ++b) {
-        for (int w = 0; w < 5; ++w) {
-            const uint8_t* p = firsts20 + 20 * b + 4 * w;
-            fp[(size_t)w * nb + b] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-        }
         uint32_t g = 0;
         for (uint32_t i = off[b]; i < off[b + 1]; ++i) g += good[i] != 0;
         gcnt[b] = g;
@@ -1418,18 +1463,13 @@ int dhtgpu_find_closest(dhtgpu_ctx* c, uint32_t nb, const uint8_t* firsts20, con
         DHT_TRY(launch_pack(c->staging.as<uint8_t>(), nn, (uint32_t*)(base + o_np), ns, c->stream));
         DHT_TRY(hipStreamSynchronize(c->stream));   // staging reused for targets
     }
-    uint64_t ts = 0;
-    DHT_TRY(c->upload_targets(t20, q, &ts));
-    DHT_TRY(c->aux2.ensure((size_t)q * count * 4));
-    DHT_TRY(c->aux3.ensure((size_t)q * 4));
-    DHT_TRY(launch_find_closest(nb, (const uint32_t*)(base + o_fp), (const uint32_t*)(base + o_off),
-                                (const uint32_t*)(base + o_g), (const uint32_t*)(base + o_np), ns,
-                                base + o_good, c->targets.as<uint32_t>(), ts, q, count,
-                                c->aux2.as<uint32_t>(), c->aux3.as<uint32_t>(), c->stream));
-    DHT_TRY(hipMemcpyAsync(out_idx, c->aux2.p, (size_t)q * count * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipMemcpyAsync(out_cnt, c->aux3.p, (size_t)q * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipStreamSynchronize(c->stream));
-    return DHTGPU_OK;
+    return host_topk(c, t20, q, count, out_idx, out_cnt,
+                     [&](const uint32_t* tp, uint64_t ts, uint32_t* d_idx, uint32_t* d_cnt) -> int {
+        DHT_TRY(launch_find_closest(nb, (const uint32_t*)(base + o_fp), (const uint32_t*)(base + o_off),
+                                    (const uint32_t*)(base + o_g), (const uint32_t*)(base + o_np), ns,
+                                    base + o_good, tp, ts, q, count, d_idx, d_cnt, c->stream));
+        return DHTGPU_OK;
+    });
 }
 
 int dhtgpu_classify_dev(const uint32_t* planes, uint64_t stride, uint64_t n, uint32_t nb,
@@ -1445,14 +1485,9 @@ int dhtgpu_classify(dhtgpu_ctx* c, uint32_t nb, const uint8_t* firsts20, const u
     if (!c || !firsts20 || !myid20 || !hist161 || nb == 0 || nb > 256) return DHTGPU_EINVAL;
     if (!c->has_ids) return DHTGPU_ENOIDS;
     DHT_TRY(c->bind());
-    std::vector<uint32_t> fp((size_t)5 * nb);
+    const std::vector<uint32_t> fp = firsts_planes(firsts20, nb);
     uint32_t my[5];
-    auto be = [](const uint8_t* p) {
-        return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-    };
-    for (uint32_t b = 0; b < nb; ++b)
-        for (int w = 0; w < 5; ++w) fp[(size_t)w * nb + b] = be(firsts20 + 20 * b + 4 * w);
-    for (int w = 0; w < 5; ++w) my[w] = be(myid20 + 4 * w);
+    for (int w = 0; w < 5; ++w) my[w] = be32(myid20 + 4 * w);
     DHT_TRY(c->aux.ensure(fp.size() * 4 + 161 * 8 + 64));
     uint8_t* base = c->aux.as<uint8_t>();
     unsigned long long* d_hist = (unsigned long long*)(base + ((fp.size() * 4 + 15) & ~size_t(15)));
@@ -1499,23 +1534,17 @@ static int cached_walk(dhtgpu_ctx* c, const uint32_t* planes, uint64_t stride, u
         d_acc = c->cache_acc.as<uint8_t>();
         DHT_TRY(hipMemcpyAsync(d_acc, accept, (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
-    uint64_t ts = 0;
-    DHT_TRY(c->upload_targets(t20, q, &ts));
-    DHT_TRY(c->aux2.ensure((size_t)q * count * 4));
-    DHT_TRY(c->aux3.ensure((size_t)q * 4));
-    DHT_TRY(launch_cached(planes, stride, n, perm, d_acc, c->targets.as<uint32_t>(), ts, q, count,
-                          c->aux2.as<uint32_t>(), c->aux3.as<uint32_t>(), c->stream));
-    if (gidx) DHT_TRY(launch_map_idx(c->aux2.as<uint32_t>(), (uint64_t)q * count, gidx, 0, c->stream));
-    DHT_TRY(hipMemcpyAsync(out_idx, c->aux2.p, (size_t)q * count * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipMemcpyAsync(out_cnt, c->aux3.p, (size_t)q * 4, hipMemcpyDeviceToHost, c->stream));
-    DHT_TRY(hipStreamSynchronize(c->stream));
-    return DHTGPU_OK;
+    return host_topk(c, t20, q, count, out_idx, out_cnt,
+                     [&](const uint32_t* tp, uint64_t ts, uint32_t* d_idx, uint32_t* d_cnt) -> int {
+        DHT_TRY(launch_cached(planes, stride, n, perm, d_acc, tp, ts, q, count, d_idx, d_cnt, c->stream));
+        if (gidx) DHT_TRY(launch_map_idx(d_idx, (uint64_t)q * count, gidx, 0, c->stream));
+        return DHTGPU_OK;
+    });
 }
 
 int dhtgpu_cached_nodes(dhtgpu_ctx* c, const uint8_t* accept, const uint8_t* t20, uint32_t q,
                         uint32_t count, uint32_t* out_idx, uint32_t* out_cnt) {
-    if (!c || count == 0 || count > DHTGPU_MAX_K || (q && (!t20 || !out_idx || !out_cnt))) return DHTGPU_EINVAL;
-    if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (int r = check_topk_host(c, t20, q, count, out_idx, out_cnt)) return r;
     DHT_TRY(c->bind());
     if (c->sorted) {
         if (!q) return DHTGPU_OK;
@@ -1542,16 +1571,9 @@ int dhtgpu_cache_set(dhtgpu_ctx* c, const uint8_t* ids20, uint64_t n, uint64_t v
     c->cache_version = 0;
     const uint64_t st = pad_ids(n ? n : 1);
     DHT_TRY(c->cache_in.ensure((size_t)st * 5 * 4));
-    const uint64_t chunk = 1ull << 22;
-    DHT_TRY(c->staging.ensure((size_t)std::min<uint64_t>(n ? n : 1, chunk) * 20));
-    for (uint64_t i = 0; i < n; i += chunk) {
-        const uint64_t m = std::min(chunk, n - i);
-        DHT_TRY(hipMemcpyAsync(c->staging.p, ids20 + i * 20, (size_t)m * 20, hipMemcpyHostToDevice, c->stream));
-        DHT_TRY(launch_pack(c->staging.as<uint8_t>(), m, c->cache_in.as<uint32_t>() + i, st, c->stream));
-        DHT_TRY(hipStreamSynchronize(c->stream));   // staging is reused
-    }
-    int r = sort_into(c, c->cache_in.as<uint32_t>(), st, n, c->cache);
+    int r = upload_ids(c, ids20, n, c->cache_in.as<uint32_t>(), st);
     if (r) return r;
+    if ((r = sort_into(c, c->cache_in.as<uint32_t>(), st, n, c->cache))) return r;
     if (!c->cache.unique) {
         c->cache.valid = false;
         return DHTGPU_EUNSORTED;
@@ -1591,7 +1613,7 @@ int dhtgpu_buffer_nodes_dev(dhtgpu_ctx* c, const uint8_t* node_tail, uint32_t af
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
     DHT_TRY(launch_wire_encode(c->planes.as<uint32_t>(), c->stride, node_tail, af == 4 ? 4u : 16u, tp, ts, q, cand,
-                               nc, out, out_len, stream ? (hipStream_t)stream : c->stream));
+                               nc, out, out_len, c->stream_or(stream)));
     return DHTGPU_OK;
 }
 
@@ -1603,7 +1625,7 @@ static int buffer_nodes_impl(dhtgpu_ctx* c, const uint32_t* planes, uint64_t str
         if (cand[i] != DHTGPU_NONE && cand[i] >= n) return DHTGPU_EINVAL;
     const uint32_t alen = af == 4 ? 4u : 16u, rec = 20 + alen + 2;
     const size_t tl = (size_t)n * (alen + 2), cl = (size_t)q * nc * 4, ol = (size_t)q * 8 * rec, ll = (size_t)q * 4;
-    DHT_TRY(c->wire.ensure(lead + al256(tl) + al256(cl) + al256(ol) + al256(ll) + 256));
+    DHT_TRY(c->wire.ensure(wire_bytes(lead, n, alen, q, nc)));
     uint8_t* base = c->wire.as<uint8_t>() + lead;
     uint8_t* d_tail = base;
     uint32_t* d_cand = reinterpret_cast<uint32_t*>(base + al256(tl));
@@ -1644,9 +1666,7 @@ int dhtgpu_buffer_nodes_ids(dhtgpu_ctx* c, const uint8_t* node_ids20, const uint
     // reallocate); the context's id set is left alone
     const uint64_t ns = pad_q(nn ? nn : 1);
     const size_t lead = al256((size_t)ns * 5 * 4);
-    const uint32_t alen = af == 4 ? 4u : 16u, rec = 20 + alen + 2;
-    DHT_TRY(c->wire.ensure(lead + al256((size_t)nn * (alen + 2)) + al256((size_t)q * nc * 4) +
-                           al256((size_t)q * 8 * rec) + al256((size_t)q * 4) + 256));
+    DHT_TRY(c->wire.ensure(wire_bytes(lead, nn, af == 4 ? 4u : 16u, q, nc)));
     if (nn) {
         DHT_TRY(c->staging.ensure((size_t)nn * 20));
         DHT_TRY(hipMemcpyAsync(c->staging.p, node_ids20, (size_t)nn * 20, hipMemcpyHostToDevice, c->stream));
@@ -1684,15 +1704,8 @@ int dhtgpu_deserialize_nodes(dhtgpu_ctx* c, uint32_t af, const uint8_t* myid20, 
     const uint64_t blen = msg_off[m];
     const size_t sz[] = {(size_t)blen, ((size_t)m + 1) * 8, ((size_t)m + 1) * 4, 32, m, (size_t)m * 16,
                          (size_t)nrec * 20, (size_t)nrec * (alen + 2), nrec};
-    size_t tot = 0;
-    for (size_t x : sz) tot += al256(x);
-    DHT_TRY(c->wire.ensure(tot));
     uint8_t* p[9];
-    uint8_t* w = c->wire.as<uint8_t>();
-    for (int i = 0; i < 9; ++i) {
-        p[i] = w;
-        w += al256(sz[i]);
-    }
+    DHT_TRY(carve(c->wire, sz, p));
     DHT_TRY(hipMemcpyAsync(p[0], blob, sz[0], hipMemcpyHostToDevice, c->stream));
     DHT_TRY(hipMemcpyAsync(p[1], msg_off, sz[1], hipMemcpyHostToDevice, c->stream));
     DHT_TRY(hipMemcpyAsync(p[2], rs.data(), sz[2], hipMemcpyHostToDevice, c->stream));
@@ -1750,15 +1763,8 @@ int dhtgpu_search_insert(dhtgpu_ctx* c, const uint8_t* node_ids20, const uint8_t
     const uint64_t ns = pad_q(nn ? nn : 1);
     const size_t sz[] = {(size_t)ns * 20, (size_t)nn, (size_t)q * cap * 4, (size_t)q * cap, (size_t)q * 4, (size_t)q,
                          ((size_t)q + 1) * 8, (size_t)m * 4, (size_t)m, (size_t)m, 16};
-    size_t tot = 0;
-    for (size_t x : sz) tot += al256(x);
-    DHT_TRY(c->srch.ensure(tot));
     uint8_t* p[11];
-    uint8_t* w = c->srch.as<uint8_t>();
-    for (int i = 0; i < 11; ++i) {
-        p[i] = w;
-        w += al256(sz[i]);
-    }
+    DHT_TRY(carve(c->srch, sz, p));
     if (nn) {
         DHT_TRY(c->staging.ensure((size_t)nn * 20));
         DHT_TRY(hipMemcpyAsync(c->staging.p, node_ids20, (size_t)nn * 20, hipMemcpyHostToDevice, c->stream));
@@ -1798,12 +1804,7 @@ int dhtgpu_table_stats(dhtgpu_ctx* c, uint32_t nb, const uint8_t* firsts20, int3
     if (!c || (nb && (!firsts20 || !out_lowbit || !out_depth))) return DHTGPU_EINVAL;
     if (!nb) return DHTGPU_OK;
     DHT_TRY(c->bind());
-    std::vector<uint32_t> fp((size_t)5 * nb);
-    for (uint32_t b = 0; b < nb; ++b)
-        for (int w = 0; w < 5; ++w) {
-            const uint8_t* q4 = firsts20 + 20 * (size_t)b + 4 * w;
-            fp[(size_t)w * nb + b] = ((uint32_t)q4[0] << 24) | ((uint32_t)q4[1] << 16) | ((uint32_t)q4[2] << 8) | q4[3];
-        }
+    const std::vector<uint32_t> fp = firsts_planes(firsts20, nb);
     const size_t a = al256(fp.size() * 4), bsz = al256((size_t)nb * 4);
     DHT_TRY(c->srch.ensure(a + 2 * bsz));
     uint8_t* base = c->srch.as<uint8_t>();
@@ -1823,9 +1824,7 @@ int dhtgpu_net_prepare(dhtgpu_ctx* c, const uint8_t* dead, uint64_t table_seed) 
     if (c->has_gidx) return DHTGPU_EINVAL;   // the network is the whole uploaded id set
     DHT_TRY(c->bind());
     // (the whole set's index whatever the accept mask says: the model has its own dead mask)
-    const dhtgpu_ctx::ActiveSet full{c->planes.as<uint32_t>(), c->stride, c->n, nullptr, nullptr, 0, 0, false,
-                                     &c->index, &c->index_B, &c->index_valid};
-    int r = index_build_on(full, c->stream, nullptr);
+    int r = index_build_on(c->full_set(), c->stream, nullptr);
     if (r) return r;
     DHT_TRY(c->net_sorted.ensure((size_t)c->n * 8));
     DHT_TRY(launch_net_sort(c->index.p, c->n, c->index_B, c->net_sorted.as<uint2>(), c->stream));
@@ -1857,7 +1856,7 @@ int dhtgpu_search_batch_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint
     DHT_TRY(launch_search(c->planes.as<uint32_t>(), c->stride, c->net_sorted.as<uint2>(), c->index.p, c->n,
                           c->index_B, c->net_has_dead ? c->net_dead.as<uint8_t>() : nullptr, c->net_seed, tp, ts, q,
                           searchers, max_rounds, c->search_alpha, out_idx, out_flags, out_len, out_rounds, out_queries,
-                          stream ? (hipStream_t)stream : c->stream));
+                          c->stream_or(stream)));
     return DHTGPU_OK;
 }
 
@@ -1873,15 +1872,8 @@ int dhtgpu_search_batch(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, const uin
     DHT_TRY(c->bind());
     const size_t L = search_list_cap();
     const size_t sz[] = {(size_t)q * 4, (size_t)q * L * 4, (size_t)q * L, (size_t)q * 4, (size_t)q * 4, (size_t)q * 4};
-    size_t tot = 0;
-    for (size_t x : sz) tot += al256(x);
-    DHT_TRY(c->net_io.ensure(tot));
     uint8_t* p[6];
-    uint8_t* w = c->net_io.as<uint8_t>();
-    for (int i = 0; i < 6; ++i) {
-        p[i] = w;
-        w += al256(sz[i]);
-    }
+    DHT_TRY(carve(c->net_io, sz, p));
     uint64_t ts = 0;
     DHT_TRY(c->upload_targets(t20, q, &ts));
     DHT_TRY(hipMemcpyAsync(p[0], searchers, sz[0], hipMemcpyHostToDevice, c->stream));

@@ -458,6 +458,50 @@ def test_three_streams_share_the_view(ctx, case2):
     ctx.set_accept(None)
 
 
+# ---- 11. closing a context ------------------------------------------------------------------
+def test_context_close_returns_device_memory():
+    """Every device buffer a context built goes back when it is closed: the id planes, the mask's
+    view and its sub-partitions, the set's sub-partitions, the K4 index, the NodeCache mirror and
+    the K6 workspaces.  Six open / use / close cycles of 2^25 ids (671 MB of planes); the first
+    loads code objects and is discarded, and the median of free-before minus free-after over the
+    other five is below half the planes' bytes.  The median, because the device is shared: a
+    neighbour's allocation shows in one cycle, a leak in every one.  The bound is a condition on
+    large buffers (a forgotten one is at least a plane set's size here): a leak of a few bytes
+    passes.  2^18 targets at k = 32, the shape of test_subpartitioned_view: with 2^17 targets one
+    K6 plan serves 2^25 ids at every k <= 32 on a 256-CU device (sub_handles_active is 0) and no
+    sub-partition would be built; the 2/3 view (22.4 M ids) is served by one plan at either count.
+    The deltas measured at the parent commit are in DESIGN.md §5f."""
+    import torch
+    import opendht_amd
+    n, q, k = 1 << 25, 1 << 18, 32
+    mask = np.ones(n, np.uint8)
+    mask[::3] = 0
+    tg = O.gen_ids(7501, q)
+    cache = O.gen_ids(7502, 1 << 16)
+    deltas = []
+    for _ in range(6):
+        torch.cuda.synchronize()
+        free_before = torch.cuda.mem_get_info(0)[0]
+        c = opendht_amd.Context(0)
+        try:
+            c.gen_ids(7500, n)
+            c.set_sub_handles(1)
+            assert c.sub_handles_active(q, k) == 1   # the shape sub-partitions on this device
+            c.set_accept(mask)
+            c.batch_topk(tg, k)      # the view (one K6 plan serves its 22.4 M ids)
+            c.set_accept(None)
+            c.batch_topk(tg, k)      # the set's sub-partitions
+            c.index_topk(tg[:64], k)   # the K4 index
+            c.cache_set(cache)
+            c.cache_nodes(tg[:64], 8)
+        finally:
+            c.close()
+        torch.cuda.synchronize()
+        deltas.append(free_before - torch.cuda.mem_get_info(0)[0])
+    print("free_before - free_after per cycle (bytes):", deltas)
+    assert float(np.median(deltas[1:])) < n * 20 / 2, deltas
+
+
 # ---- the C++ adapter ------------------------------------------------------------------------
 def test_cpp_accept_adapter_on_gpu(tmp_path):
     """ClosestIndex::set_accept_good + query against a host brute force with detail::xor_closer
