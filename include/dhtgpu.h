@@ -245,7 +245,11 @@ int dhtgpu_index_topk(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, 
  * workspaces and gives each stream its own (the one it last used, else a free one), so calls
  * issued on up to four streams run concurrently (one batch's latency-bound answer phase
  * overlaps the other batches' HBM-bound id streams); a call that must take a workspace last
- * used on another stream (a fifth stream) first waits for that stream. */
+ * used on another stream (a fifth stream) first waits for that stream.
+ * Alignment: out_idx, out_cnt and out_rec need 4-byte alignment only (rows on a 16-byte
+ * boundary are stored as whole vectors, others word by word: the same results), and the target
+ * planes are read one word at a time, so t_planes needs 4-byte alignment and t_stride may be any
+ * value >= q (odd ones included). */
 int dhtgpu_batch_topk_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_stride, uint32_t q,
                           uint32_t k, uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec,
                           uint32_t idx_base, void* stream);
@@ -258,6 +262,23 @@ int dhtgpu_batch_topk_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_
 int dhtgpu_batch_topk_timed(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_stride, uint32_t q,
                             uint32_t k, uint32_t* out_idx, uint32_t* out_cnt, void* stream, float* ms4,
                             uint32_t* stats4);
+/* Diagnostics, host only (no device work; ctx may be NULL): the plan a dhtgpu_batch_topk* call of
+ * q targets at k over a set of n ids would run with -- on ctx's device (num_cus ignored), or with
+ * ctx == NULL on a device of num_cus compute units.  n is the number of ids the call answers from
+ * (the accepted ids while a mask is set).  out[16]:
+ *    0  route: 0 = KS small batch, 1 = K6 over one set, 2 = K6 over sub-partitions, 3 = refused
+ *              (DHTGPU_ERANGE from the call)
+ *    1  Lm, the mark level           2  Lmin, the coarsest level a target answers from
+ *    3  b1, partition bits           4  Lq, the deepest level F3 sorts by
+ *    5  tcap, targets per partition bucket       6  scap, survivors per (bucket set, partition)
+ *    7  nsets, bucket sets per partition         8  F3 stage entries of the launch
+ *    9  F2 mode: 0 dense, 1 sparse, 3 segmented, 4 narrow stage
+ *   10  F2 stage entries of the launch          11  ids per F2 workgroup
+ *   12  F2 workgroups               13  1 when F1 runs as coarse + fine passes
+ *   14  KS level Ls (route 0 only)  15  0
+ * Words 1..13 are defined for route 1 only (0 otherwise): a sub-partitioned call's plan depends
+ * on the sub-partitions built from the set. */
+int dhtgpu_batch_plan(dhtgpu_ctx* ctx, int num_cus, uint64_t n, uint32_t q, uint32_t k, uint32_t out[16]);
 /* Arm per-kernel timing of the NEXT K6 call on this context without synchronising it:
  * its kernels' own dispatches record start/stop into ev8[0..7] (hipEvent_t as void*, created
  * by the caller with timing enabled) = {F1 start, F1 stop, F2 start, F2 stop, F3 .., F4 ..}

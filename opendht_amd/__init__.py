@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-__all__ = ["Context", "DhtGpuError", "NONE", "MAX_K", "lib", "LIB_PATH", "id_words"]
+__all__ = ["Context", "DhtGpuError", "NONE", "MAX_K", "lib", "LIB_PATH", "id_words", "batch_plan"]
 
 # DHTGPU_LIB: another build of the same library (A/B experiments, tools/experiments/gpu_ab_lib.sh)
 LIB_PATH = os.environ.get("DHTGPU_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdhtgpu.so")
@@ -121,6 +121,8 @@ def lib():
         "dhtgpu_batch_topk_timed": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
                                      ctypes.POINTER(ctypes.c_float), _u32p], ctypes.c_int),
         "dhtgpu_batch_topk": ([_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_batch_plan": ([_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u32p],
+                              ctypes.c_int),
         "dhtgpu_table_depth": ([ctypes.c_uint32, _u8p, ctypes.c_uint32, _u32p], ctypes.c_int),
         "dhtgpu_buffer_nodes_dev": ([_vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp,
                                      ctypes.c_uint32, _vp, _vp, _vp], ctypes.c_int),
@@ -159,7 +161,7 @@ def exported_symbols():
             "dhtgpu_sub_handles_active", "dhtgpu_handles_to_indices_dev", "dhtgpu_set_search_alpha", "dhtgpu_cache_set",
             "dhtgpu_cache_nodes", "dhtgpu_cache_sorted", "dhtgpu_buffer_nodes_ids", "dhtgpu_batch_events",
             "dhtgpu_search_insert", "dhtgpu_table_stats", "dhtgpu_set_accept", "dhtgpu_set_accept_bits_dev",
-            "dhtgpu_update_accept", "dhtgpu_num_accepted", "dhtgpu_write_ids"]
+            "dhtgpu_update_accept", "dhtgpu_num_accepted", "dhtgpu_write_ids", "dhtgpu_batch_plan"]
 
 
 def _ids(a, name="ids"):
@@ -579,6 +581,23 @@ def table_depth(firsts, b):
     d = ctypes.c_uint32()
     _check(lib().dhtgpu_table_depth(f.shape[0], _p(f, _u8p), b, ctypes.byref(d)), "table_depth")
     return d.value
+
+
+PLAN_FIELDS = ("route", "Lm", "Lmin", "b1", "Lq", "tcap", "scap", "nsets", "f3_stage", "f2_mode", "f2_stage",
+               "per_blk", "nblk2", "f1_two_pass", "Ls")
+ROUTE_KS, ROUTE_K6, ROUTE_SUBS, ROUTE_REFUSED = 0, 1, 2, 3
+F2_DENSE, F2_SPARSE, F2_SEG, F2_NARROW = 0, 1, 3, 4
+
+
+def batch_plan(n, q, k, ctx=None, num_cus=256):
+    """The plan a batch_topk call of q targets at k over n ids runs with (host only, no device
+    work): a dict of PLAN_FIELDS (include/dhtgpu.h, dhtgpu_batch_plan).  ctx: a Context, whose
+    device's CU count is used; else num_cus.  Fields past `route` are defined for ROUTE_K6 (Ls for
+    ROUTE_KS) and 0 otherwise."""
+    out = (ctypes.c_uint32 * 16)()
+    _check(lib().dhtgpu_batch_plan(ctx._h if ctx is not None else None, int(num_cus), int(n), int(q), int(k), out),
+           "batch_plan")
+    return {name: int(out[i]) for i, name in enumerate(PLAN_FIELDS)}
 
 
 def device_count():

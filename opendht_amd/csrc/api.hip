@@ -669,7 +669,7 @@ int dhtgpu_set_sub_handles(dhtgpu_ctx* c, int on) {
     return DHTGPU_OK;
 }
 
-static bool needs_subs(const dhtgpu_ctx* c, uint64_t n, uint32_t q, uint32_t k);
+static bool needs_subs(int num_cus, uint64_t n, uint32_t q, uint32_t k);
 
 // measurement only (not in include/): the phase-stamp buffer of DHTGPU_DBG=256 runs
 int dhtgpu_debug_stamps(dhtgpu_ctx* c, void** dev_ptr, uint64_t* bytes) {
@@ -790,7 +790,7 @@ int dhtgpu_write_ids(dhtgpu_ctx* c, uint64_t first, const uint8_t* ids20, uint64
 int dhtgpu_sub_handles_active(dhtgpu_ctx* c, uint32_t q, uint32_t k) {
     if (!c || !c->has_ids) return 0;
     if (c->acc.has_mask) return 0;   // masked calls return indices
-    return c->sub_handles && !(small_supported(c->n, q, k) && !(c->dbg & (1u << 23))) && needs_subs(c, c->n, q, k) ? 1 : 0;
+    return c->sub_handles && !(small_supported(c->n, q, k) && !(c->dbg & (1u << 23))) && needs_subs(c->num_cus, c->n, q, k) ? 1 : 0;
 }
 
 int dhtgpu_handles_to_indices_dev(dhtgpu_ctx* c, const uint32_t* handles, uint64_t m, uint32_t* out_idx,
@@ -1338,8 +1338,8 @@ static int small_run(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32
     return DHTGPU_OK;
 }
 
-static bool needs_subs(const dhtgpu_ctx* c, uint64_t n, uint32_t q, uint32_t k) {
-    return n > (1ull << 24) && !batch_supported(n, q, k, c->num_cus) && q <= (1u << 22);
+static bool needs_subs(int num_cus, uint64_t n, uint32_t q, uint32_t k) {
+    return n > (1ull << 24) && !batch_supported(n, q, k, num_cus) && q <= (1u << 22);
 }
 
 static int batch_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k, uint32_t* out_idx,
@@ -1360,7 +1360,7 @@ static int batch_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q,
     if (small_supported(A.n, q, k) && !(c->dbg & (1u << 23)))
         return small_run(c, A, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s, ev);
     c->last_small = false;
-    if (needs_subs(c, A.n, q, k)) return batch_run_subs(c, A, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s, ev);
+    if (needs_subs(c->num_cus, A.n, q, k)) return batch_run_subs(c, A, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base, s, ev);
     if (!batch_supported(A.n, q, k, c->num_cus)) return DHTGPU_ERANGE;
     const int si = pick_slot(c, s);
     dhtgpu_ctx::BatchSlot& b = c->bslot[si];
@@ -1406,6 +1406,26 @@ int dhtgpu_batch_topk_timed(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint
     } else if (stats4) {
         DHT_TRY(batch_read_stats(c->bslot[c->blast].ws.p, c->last_n, q, c->last_qp, k, c->num_cus, stats4, s,
                                  c->last_nsub, c->last_pf));
+    }
+    return DHTGPU_OK;
+}
+
+int dhtgpu_batch_plan(dhtgpu_ctx* c, int num_cus, uint64_t n, uint32_t q, uint32_t k, uint32_t* out16) {
+    if (!out16 || k == 0 || k > DHTGPU_MAX_K || !q || !n) return DHTGPU_EINVAL;
+    const int cus = c ? c->num_cus : num_cus;
+    const uint32_t dbg = c ? c->dbg : 0u;
+    for (int i = 0; i < 16; ++i) out16[i] = 0;
+    // batch_run's order of decisions
+    if (small_supported(n, q, k) && !(dbg & (1u << 23))) {
+        out16[0] = 0;
+        out16[14] = small_level(n, k);
+    } else if (needs_subs(cus, n, q, k)) {
+        out16[0] = 2;
+    } else if (!batch_supported(n, q, k, cus)) {
+        out16[0] = 3;
+    } else {
+        out16[0] = 1;
+        batch_plan_words(n, q, k, cus, out16);
     }
     return DHTGPU_OK;
 }

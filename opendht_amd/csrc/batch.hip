@@ -2384,6 +2384,38 @@ uint32_t deal_f2_blocks(const BatchPlan& P, const SubSpec* subs, uint32_t nsub, 
     return blk;
 }
 
+// What a launch does with its plan once F2's workgroups are dealt (launch_batch_topk; the plan
+// query dhtgpu_batch_plan reports the same values): whether some workgroup's range spans more
+// than one segment, whether F2 runs the narrow stage, F2's mode among the stage-sorting
+// instantiations (window and direct forms are chosen by the caller), the stage entries F2 and
+// F3 are given, and whether F1 runs as coarse + fine.
+struct BatchRoute {
+    bool seg_used, narrow, f1_two_pass;
+    uint32_t f2_mode, f2_stage, f3_cap;
+    F1Coarse f1c;
+};
+BatchRoute route_batch(const BatchPlan& P, const BatchPlan& P0, const SubDesc* hd, uint32_t nsub, uint32_t seg,
+                       bool direct, uint32_t q, uint32_t q_plan) {
+    BatchRoute R{};
+    for (uint32_t i = 0; i < nsub; ++i) R.seg_used = R.seg_used || (hd[i].nblk && hd[i].per_blk > seg);
+    // the narrow stage: every workgroup's range under 2^16 ids and its survivors (mean + 8 sigma
+    // + 256 on uniform ids) within the narrow stage; no segments
+    R.narrow = !direct && P.nstage && P.sparse && !R.seg_used;
+    {
+        const double f = 1.0 - std::exp(-(double)q_plan / (double)(1ull << P.Lm));
+        for (uint32_t i = 0; i < nsub && R.narrow; ++i) {
+            const double mean = (double)hd[i].per_blk * f, sd = std::sqrt(mean * P.clump);
+            if (hd[i].nblk && (hd[i].per_blk > 65536 || mean + 8.0 * sd + 256.0 > (double)P.nstage)) R.narrow = false;
+        }
+    }
+    R.f2_mode = R.narrow ? kF2Narrow : P.sparse && R.seg_used ? kF2Seg : P.sparse ? kF2Sparse : kF2Dense;
+    R.f2_stage = R.narrow ? P.nstage : P.stage;
+    R.f3_cap = R.narrow ? P.f3cap : P.f3cap_wide;
+    R.f1c = f1_coarse(P0, nsub, q);
+    R.f1_two_pass = R.f1c.nbins && P.Lm == P0.Lm && P.b1 == P0.b1;
+    return R;
+}
+
 }  // namespace
 
 bool batch_supported(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t nsub, uint32_t pf) {
@@ -2681,19 +2713,9 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
         }
     }
     const bool win = P.wwords != 0;
-    bool seg_used = false;   // some workgroup's range spans more than one segment
-    for (uint32_t i = 0; i < nsub; ++i) seg_used = seg_used || (hd[i].nblk && hd[i].per_blk > seg);
     if (nblk2 > kMaxF2Blocks) return hipErrorInvalidValue;
-    // the narrow stage: every workgroup's range under 2^16 ids and its survivors (mean + 8 sigma
-    // + 256 on uniform ids) within the narrow stage; no segments
-    bool narrow = !direct && P.nstage && P.sparse && !seg_used;
-    {
-        const double f = 1.0 - std::exp(-(double)c.q_plan / (double)(1ull << P.Lm));
-        for (uint32_t i = 0; i < nsub && narrow; ++i) {
-            const double mean = (double)hd[i].per_blk * f, sd = std::sqrt(mean * P.clump);
-            if (hd[i].nblk && (hd[i].per_blk > 65536 || mean + 8.0 * sd + 256.0 > (double)P.nstage)) narrow = false;
-        }
-    }
+    const BatchRoute R = route_batch(P, P0, hd, nsub, seg, direct, q, c.q_plan);
+    const bool narrow = R.narrow;
     if (NP > 8192 || nblk2 > 8192) dbg &= ~256u;   // phase stamps hold 8192 workgroups per kernel
     if (nsub > 1) {
         uint64_t sig = 1469598103934665603ull;
@@ -2733,8 +2755,8 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
     if (dbg & 256) (void)hipMemsetAsync(stamps, 0, (size_t)3 * 8192 * 16 * 8, s);
     const F1Args a1{c.tp, c.tp + c.ts, q, P.Lm, P.b1, c.skip, c.sub_shift, c.nsub ? c.sub_bits : 0u, np, P.nwords,
                     bitmap, tcount, tbuf, P.tcap, ctr, tspill, P.sib ? c.cells : nullptr, k};
-    const F1Coarse f1c = f1_coarse(P0, nsub, q);
-    if (f1c.nbins && P.Lm == P0.Lm && P.b1 == P0.b1) {
+    const F1Coarse& f1c = R.f1c;
+    if (R.f1_two_pass) {
         F1cArgs ac{c.tp, c.tp + c.ts, q, c.skip, c.sub_shift, c.nsub ? c.sub_bits : 0u, f1c.c, f1c.ccap,
                    reinterpret_cast<uint32_t*>(w + Ly.ccount), reinterpret_cast<uint2*>(w + Ly.cbuf),
                    P.Lm, P.b1, np, P.nwords, bitmap, tcount, tbuf, P.tcap, ctr, tspill,
@@ -2753,7 +2775,7 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
     }
     if (nblk2) {
         F2Args a2{d_desc, d_blk, hd[0], nsub, NP, P.Lm, P.b1, bitmap, P.nwords, pcount, pbuf, P.scap, ctr,
-                  narrow ? P.nstage : P.stage, dbg, P.sparse, seg, (dbg & 256) ? stamps + 8192 * 16 : stamps};
+                  R.f2_stage, dbg, P.sparse, seg, (dbg & 256) ? stamps + 8192 * 16 : stamps};
         a2.nsets = P.nsets;
         a2.wwords = P.wwords;
         a2.pk_ob = pk_ob;
@@ -2772,9 +2794,9 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
         else if (win && nt) go(1, k_f2_filter<kF2Sparse, kF2SubsNT, true>, g2, b2, l2, a2);
         else if (win && !P.wpack) go(1, k_f2_filter<kF2Seg, kF2Subs, true>, g2, b2, l2, a2);
         else if (win) go(1, k_f2_filter<kF2Sparse, kF2Subs, true>, g2, b2, l2, a2);
-        else if (narrow) F2_GO(kF2Narrow);
-        else if (P.sparse && seg_used) F2_GO(kF2Seg);
-        else if (P.sparse) F2_GO(kF2Sparse);
+        else if (R.f2_mode == kF2Narrow) F2_GO(kF2Narrow);
+        else if (R.f2_mode == kF2Seg) F2_GO(kF2Seg);
+        else if (R.f2_mode == kF2Sparse) F2_GO(kF2Sparse);
         else F2_GO(kF2Dense);
 #undef F2_GO
     } else if (ev) {
@@ -2784,7 +2806,7 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
     // the base arguments are the whole set's: F4's scan (fallback targets) runs over all its ids
     F3Args a{pbuf, pcount, P.scap, tbuf, tcount, P.tcap, tspill, P.Lm, P.b1, P.Lq, bitmap, P.nwords, c.planes, c.stride,
              c.n, c.tp, c.ts, k, c.gidx, c.base, c.out_idx, c.out_cnt, ctr, fb_list, fb_sub, pstat, tie_hdr, tie_cand, tie_cnt,
-             d_desc, np, dbg, stamps, narrow ? P.f3cap : P.f3cap_wide, RecOut{}, P.Lm - P.sib, P.nsets};
+             d_desc, np, dbg, stamps, R.f3_cap, RecOut{}, P.Lm - P.sib, P.nsets};
     if (c.out_rec)
         a.rec = RecOut{c.out_rec, c.planes, c.stride, c.rec_gidx, c.rec_base, (nsub == 1 && !c.w0s && !c.skip) ? 1u : 0u,
                        c.skip && c.skip < 32 ? c.skip : 0u, c.nsub ? c.pval << c.sub_bits : c.pval};
@@ -3189,6 +3211,37 @@ __global__ __launch_bounds__(kS2Threads) void k_s2_answer(F3Args a, SmallArgs sa
 // F4 scratch for a list scan: done counters | split records
 static size_t list_scan_bytes(uint32_t k) { return al256((size_t)kFbBlocks * 4) + al256((size_t)kFbBlocks * kFbGroup * k * 24); }
 
+// KS's level: the deepest with >= 4k ids per subtree on uniform ids (K6's rule), at most 31
+uint32_t small_level(uint64_t n, uint32_t k) {
+    uint32_t Ls = 0;
+    while (Ls < 31 && (n >> (Ls + 1)) >= 4ull * k) ++Ls;
+    return Ls;
+}
+
+// The one-set K6 plan of (n, q, k) as a launch on num_cus CUs would use it: words 1..13 of
+// dhtgpu_batch_plan (include/dhtgpu.h).  Host only.
+void batch_plan_words(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t* out) {
+    const BatchPlan P = plan_batch(n, q, k, num_cus, 0);
+    const SubSpec one{nullptr, nullptr, pad_ids(n), n, nullptr, 0u};
+    SubDesc hd[1];
+    uint32_t seg = 0;
+    const uint32_t nblk2 = deal_f2_blocks(P, &one, 1, q, num_cus, hd, &seg);
+    const BatchRoute R = route_batch(P, P, hd, 1, seg, false, q, q);
+    out[1] = P.Lm;
+    out[2] = P.Lm - P.sib;
+    out[3] = P.b1;
+    out[4] = P.Lq;
+    out[5] = P.tcap;
+    out[6] = P.scap;
+    out[7] = P.nsets;
+    out[8] = R.f3_cap;
+    out[9] = R.f2_mode;
+    out[10] = R.f2_stage;
+    out[11] = (uint32_t)hd[0].per_blk;
+    out[12] = nblk2;
+    out[13] = R.f1_two_pass ? 1u : 0u;
+}
+
 bool small_supported(uint64_t n, uint32_t q, uint32_t k) {
     return q >= 1 && q <= kSmallQ && k >= 1 && k <= DHTGPU_MAX_K_DEV && n >= 1 && n < (1ull << 31);
 }
@@ -3214,9 +3267,7 @@ hipError_t launch_small_topk(const BatchCall& c, void* sws, uint32_t parity, hip
     x += list_scan_bytes(DHTGPU_MAX_K_DEV);
     a.cand = reinterpret_cast<uint4*>(x);
     const uint64_t n = c.n;
-    // level: the deepest with >= 4k ids per subtree on uniform ids (K6's rule), at most 31
-    a.Ls = 0;
-    while (a.Ls < 31 && (n >> (a.Ls + 1)) >= 4ull * c.k) ++a.Ls;
+    a.Ls = small_level(n, c.k);
     a.w0 = c.w0s ? c.w0s : c.planes;
     a.w1 = c.planes + c.stride;
     a.n = n;

@@ -233,6 +233,10 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s);
 // zero); parity: alternates between consecutive calls on one workspace (two counter sets);
 // ev (nullable) gets S1 as F2's pair and S2 as F3's, F1 / F4 pairs empty.
 bool small_supported(uint64_t n, uint32_t q, uint32_t k);
+uint32_t small_level(uint64_t n, uint32_t k);   // KS's prefix level Ls
+// words 1..13 of dhtgpu_batch_plan (include/dhtgpu.h) for a one-set K6 call that batch_supported
+// accepts: the plan and what launch_batch_topk makes of it, from the launch's own functions
+void batch_plan_words(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t* out16);
 size_t small_bytes();
 hipError_t launch_small_topk(const BatchCall& c, void* sws, uint32_t parity, hipStream_t s);
 
