@@ -33,14 +33,16 @@
 // Algorithmic bytes per call: n * 4 (w0) + q * 4 (target w0) + survivors * 16 (written
 // and re-read as {w0, idx}) + q * k * 4 (results).  On uniform ids the survivor fraction
 // is 1 - exp(-q / 2^Lm) (12 % at the cfg-2 batch).
+//
+// This file holds the kernels and what calls HIP.  The plan of a call, its workspace layout and
+// every decision of a launch are host-only code in batch_plan.cpp (decide_batch); batch_plan.h
+// holds the constants and structures both sides share.
 #include "scan_dev.h"
 #include <hip/hip_ext.h>
 
 #include <mutex>
 
 #include <algorithm>
-#include <cmath>
-#include <cstdlib>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -48,26 +50,11 @@
 namespace dhtgpu {
 namespace {
 
-constexpr int kF1Threads = 256;                      // one thread per target
-constexpr int kF3Threads = 256;
-constexpr uint32_t kF3Cap = 4096;                    // survivors per partition staged in LDS
+static_assert(kMaxK == DHTGPU_MAX_K_DEV, "batch_plan.h: kMaxK");
+static_assert(kFbGroup == scan::WAVES * kScanTargets, "batch_plan.h: kFbGroup (targets per scan role)");
 constexpr uint32_t kF3Per = kF3Cap / kF3Threads;
-constexpr uint32_t kMaxLm = 19;                      // 2^19-bit bitmap = 64 KB of LDS in F2
-constexpr uint32_t kMaxSubBits = 11;                 // F3 sub-prefix histogram <= 2048 bins
-constexpr uint32_t kMaxQ = 1u << 22;                 // targets per call
-constexpr uint32_t kTieSlots = 8;                    // deferred-tie slots per F3 partition
-// F1's per-target bucket counters tcount[p] sit 256 B apart: their returning atomics execute
-// at the memory side, one request per lane (random partitions), and counters packed into one
-// 4 KB run would all queue on the same channel.  F2's pcount stays packed: its flush reserves
-// consecutive partitions from consecutive lanes, which coalesce into one request per line.
-// F2's survivor buckets come in kSets sets, one per XCD (block b uses set b % 8: blocks b and
-// b + 8 share an XCD): a counter then takes 32 blocks' reservations instead of 256 (one
-// address completes about 88 returning atomics per µs), and a bucket's partial-line runs are
-// all written through one XCD's L2, which merges them into whole lines.  F3 gathers a
-// partition from its kSets contiguous buckets.
-constexpr uint32_t kSets = 8;
-constexpr uint32_t kCtrStride = 64;
-constexpr uint32_t kLdsMax = 160 * 1024;
+constexpr uint32_t kLdsMax = kLdsBytes;
+inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 
 __device__ __forceinline__ uint32_t top_bits(uint32_t w, uint32_t b) { return b ? w >> (32 - b) : 0u; }
 
@@ -162,24 +149,6 @@ __device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c)
 // ctr[kSpill]); F3 moves the spill list to the F4 fallback list.
 constexpr uint32_t kSpill = 8;   // ctr word: spilled targets (all-zero between calls)
 
-// Prefix sub-partitions (dhtgpu_ctx: a set too large for one plan is split by the next
-// sub_bits id bits after its shard prefix, each part compacted with its own shifted word-0
-// plane): ONE launch sequence serves all of them.  A target's sub-partition is its bits
-// [sub_shift, sub_shift + sub_bits); every sub-partition has its own bitmap and its own np
-// partitions (global partition = sub * np + p); F2's workgroups are dealt to the
-// sub-partitions in proportion to their ids; F3 / F4 read the tie words and map the results
-// through the target's sub-partition.  A set that needs no split is the one sub-partition.
-struct SubDesc {
-    const uint32_t* w0;       // streamed word-0 plane (shifted for shards / sub-partitions)
-    const uint32_t* planes;   // unshifted word planes (tie words)
-    uint64_t stride, n;
-    const uint32_t* gidx;     // result index map (nullable) ...
-    uint32_t base;            // ... or offset
-    uint32_t lim;             // last 16-B aligned word offset loadable inside w0's allocation
-    uint32_t blk0, nblk;      // its F2 workgroups
-    uint64_t per_blk;         // F2 ids per workgroup
-};
-
 struct F1Args {
     const uint32_t* tw0; const uint32_t* tw1;
     uint32_t q, Lm, b1, shift;
@@ -231,13 +200,7 @@ __global__ __launch_bounds__(kF1Threads) void k_f1_targets(F1Args a) {
 //                    tbuf[p][rank], then writes its bitmap words and partition counts with plain
 //                    stores (every word and count of the bin, zeros included).
 // A bin or bucket past its capacity spills the target to the F4 fallback list, as F1 does.
-constexpr uint32_t kF1aThreads = 1024, kF1aPer = 4, kF1aTargets = kF1aThreads * kF1aPer;
-constexpr uint32_t kF1bThreads = 1024, kF1bPer = 4;
-constexpr uint32_t kMaxCoarse = 4096;             // bins (the coarse counters live in the clean head)
-constexpr uint32_t kF1bLdsWords = 16384;          // F1b's bitmap words + partition counts (64 KB)
-constexpr uint32_t kF1CoarseMinQ = 1u << 17;      // smaller batches: k_f1_targets (at 2^17 F1 is as fast either
-                                                  // way, 13.1-13.4 us, and the two-pass form leaves the other call
-                                                  // in flight the atomics: prefix rank 0.130-0.135 -> 0.127-0.128 ms)
+constexpr uint32_t kF1bThreads = 1024, kF1bPer = 4;   // (F1a's shape and the bin limits: batch_plan.h)
 
 struct F1cArgs {
     const uint32_t* tw0; const uint32_t* tw1;
@@ -354,19 +317,6 @@ __global__ __launch_bounds__(kF1bThreads) void k_f1_fine(F1cArgs a) {
 // a ring of kF2Ring 16-B loads per lane (32 KB in flight per CU).  Survivors are appended
 // to an LDS stage; when the stage could overflow (and at the end) it is flushed into the
 // partition-major survivor buckets pbuf[p][...] (see f2_flush).
-constexpr int kF2Threads = 1024;
-constexpr uint32_t kF2Sub = 4 * kF2Threads;          // ids per sub-step (one uint4 per thread)
-constexpr uint32_t kF2Step = 4 * kF2Sub;             // ids per chunk
-constexpr uint32_t kStage = 11264;                   // LDS stage entries (88 KB)
-// window mode (prefix-sorted sub-partitions: a workgroup's bitmap is the window of words its
-// sorted range spans, a few KB instead of 64): the stage takes the freed LDS when one final flush
-// then holds the workgroup's survivors (the cfg-3 shard: 16.2 K per workgroup, two flushes before)
-constexpr uint32_t kStageWin = 25600;
-
-__host__ __device__ inline uint32_t f2_fixed_words(uint32_t nwords, uint32_t np) {
-    return (36 + nwords + np + 1 + 17 + np / 32 + 1 + 3) & ~3u;
-}
-
 struct F2Args {
     const SubDesc* subs; const uint8_t* blk_sub;   // sub-partitions; workgroup -> sub-partition
     SubDesc one; uint32_t nsub;                    // nsub == 1: the one sub-partition (no table loads)
@@ -383,8 +333,7 @@ struct F2Args {
     uint32_t seg;                 // sparse mode: ids per segment (the stage is flushed after each)
     unsigned long long* stamps;   // dbg & 256: per-block phase timestamps [nblk2][16]
     uint32_t nsets;               // kSets, or 1 over prefix-sorted sub-partitions (a partition's survivors come from one or two workgroups)
-    uint32_t wwords;              // window mode: bitmap words in LDS (the window from the range's first word)
-    uint32_t pk_ob;               // window + Sparse: index-offset bits of the packed stage (StagePk)
+    uint32_t wwords;              // k_f2_direct: bitmap words in LDS (the window from the range's first word)
 };
 #define F2_STAMP(i) \
     do { if ((a.dbg & 256) && threadIdx.x == 0) a.stamps[(uint64_t)blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -399,117 +348,35 @@ struct F2Args {
 // [a.stage] u32 then the id's offset from the workgroup's first id [a.stage] u16 -- 6 B per
 // entry instead of 8, so F2's LDS leaves room for an F3 workgroup of another batch on its CU.
 constexpr uint32_t kStagePer = (kStage + 1023) / 1024;
-constexpr uint32_t kStagePerWin = (kStageWin + 1023) / 1024;
-// Packed stage (window mode, Sparse): the same two arrays, holding the 48-bit value
-// (w0 - wb0) << ob | (index - the workgroup's first id): a sorted workgroup range spans a few
-// thousand bitmap words, so its word 0 minus the window's first word fits 48 - ob bits (the host
-// checks) -- the stage of the cfg-3 shard's 16 K-survivor ranges then fits one final flush.
-struct StagePk { uint32_t wb0, ob; };
-template <int Fmt>   // 0: 8-B {w0, index}; 1: narrow (u32 w0, u16 offset); 2: packed
-__device__ __forceinline__ uint2 stage_get(const uint2* stage, uint32_t cap, uint32_t ibase, uint32_t j, StagePk pk) {
+template <int Fmt>   // 0: 8-B {w0, index}; 1: narrow (u32 w0, u16 offset)
+__device__ __forceinline__ uint2 stage_get(const uint2* stage, uint32_t cap, uint32_t ibase, uint32_t j) {
     if (Fmt == 0) return stage[j];
     const uint32_t* sw = reinterpret_cast<const uint32_t*>(stage);
     const uint16_t* si = reinterpret_cast<const uint16_t*>(sw + cap);
-    if (Fmt == 1) return make_uint2(sw[j], ibase + si[j]);
-    const uint64_t v = (uint64_t)si[j] << 32 | sw[j];
-    return make_uint2(pk.wb0 + (uint32_t)(v >> pk.ob), ibase + (uint32_t)(v & ((1ull << pk.ob) - 1ull)));
+    return make_uint2(sw[j], ibase + si[j]);
 }
 template <int Fmt>
-__device__ __forceinline__ void stage_put(uint2* stage, uint32_t cap, uint32_t ibase, uint32_t j, uint32_t w, uint32_t i,
-                                          StagePk pk) {
+__device__ __forceinline__ void stage_put(uint2* stage, uint32_t cap, uint32_t ibase, uint32_t j, uint32_t w, uint32_t i) {
     if (Fmt == 0) { stage[j] = make_uint2(w, i); return; }
     uint32_t* sw = reinterpret_cast<uint32_t*>(stage);
     uint16_t* si = reinterpret_cast<uint16_t*>(sw + cap);
-    if (Fmt == 1) {
-        sw[j] = w;
-        si[j] = (uint16_t)(i - ibase);
-        return;
-    }
-    const uint64_t v = (uint64_t)(w - pk.wb0) << pk.ob | (i - ibase);
-    sw[j] = (uint32_t)v;
-    si[j] = (uint16_t)(v >> 32);
+    sw[j] = w;
+    si[j] = (uint16_t)(i - ibase);
 }
-// Agg (window mode): a sorted range's survivors sit in the stage in stream order, so wave w's
-// contiguous chunk [w C, (w + 1) C) of it holds one or two partitions.  No stage sort: the wave
-// ranks its entries per partition in registers (up to 4 partitions a round), reserves each
-// partition's share of its bucket with one returning atomic per (wave, partition) -- all of a
-// round's in one instruction -- and stores the entries there itself.  (Sorting a sorted stage by
-// per-entry LDS atomics on one or two addresses serialised: the window's single flush of 15 K
-// entries spent 6 us ranking them.)
-template <int Fmt, uint32_t Per = kStagePer, bool Agg = false>
+template <int Fmt>
 __device__ void f2_flush(const F2Args& a, uint32_t cnt, uint2* stage, uint32_t* hist, uint32_t* wsum, uint32_t poff,
-                         uint32_t ibase, StagePk pk = StagePk{0u, 0u}) {
+                         uint32_t ibase) {
+    constexpr uint32_t Per = kStagePer;
     const uint32_t np = 1u << a.b1;
     uint2 e[Per];
     uint32_t rk[Per];
-    const uint32_t lane = lane_id();
-    if (Agg) {
-        const uint32_t w = threadIdx.x >> 6;
-        const uint32_t C = (cnt + kF2Threads - 1) / kF2Threads * 64;   // entries per wave (<= Per * 64)
-        uint32_t valid = 0;   // bit r: slice r holds an entry for this lane
-#pragma unroll
-        for (uint32_t r = 0; r < Per; ++r) {
-            const uint32_t j = w * C + r * 64 + lane;
-            if (r * 64 < C && j < cnt) {
-                e[r] = stage_get<Fmt>(stage, a.stage, ibase, j, pk);
-                valid |= 1u << r;
-            }
-        }
-        F2_STAMP(6);
-        sync_lds();   // every entry is in registers: the caller may refill the stage after this flush
-        const uint32_t set = a.nsets == 1 ? 0u : blockIdx.x % kSets, set_off = set * a.np_all + poff;
-        for (;;) {   // wave-uniform rounds of up to 4 partitions (one round on sorted uniform ids)
-            uint32_t tk[4] = {DHT_NONE, DHT_NONE, DHT_NONE, DHT_NONE}, tc[4] = {0u, 0u, 0u, 0u}, nt = 0, pend = 0;
-#pragma unroll
-            for (uint32_t r = 0; r < Per; ++r) {
-                const bool v = (valid >> r) & 1u;
-                const uint32_t key = v ? top_bits(e[r].x, a.b1) : DHT_NONE;
-                uint64_t act = __ballot(v);
-                while (act) {
-                    const uint32_t kk = (uint32_t)__builtin_amdgcn_readlane((int)key, __ffsll((long long)act) - 1);
-                    const uint64_t m = __ballot(key == kk) & act;
-                    act &= ~m;
-                    uint32_t q = 4;
-#pragma unroll
-                    for (uint32_t x = 0; x < 4; ++x) q = (x < nt && tk[x] == kk) ? x : q;
-                    if (q == 4 && nt < 4) { q = nt++; tk[q] = kk; }
-                    if (q == 4) continue;   // a fifth partition: the next round
-                    if ((m >> lane) & 1ull) {
-                        rk[r] = (tc[q] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) | (q << 28);
-                        pend |= 1u << r;
-                    }
-                    tc[q] += (uint32_t)__popcll(m);
-                }
-            }
-            if (nt == 0) break;
-            uint32_t res = 0;
-            if (lane < nt) {
-                const uint32_t kq = lane == 0 ? tk[0] : lane == 1 ? tk[1] : lane == 2 ? tk[2] : tk[3];
-                const uint32_t cq = lane == 0 ? tc[0] : lane == 1 ? tc[1] : lane == 2 ? tc[2] : tc[3];
-                res = atomicAdd(a.pcount + set_off + kq, cq);
-            }
-            const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)res, 0), b1 = (uint32_t)__builtin_amdgcn_readlane((int)res, 1);
-            const uint32_t b2 = (uint32_t)__builtin_amdgcn_readlane((int)res, 2), b3 = (uint32_t)__builtin_amdgcn_readlane((int)res, 3);
-#pragma unroll
-            for (uint32_t r = 0; r < Per; ++r) {
-                if (!((pend >> r) & 1u)) continue;
-                const uint32_t q = rk[r] >> 28;
-                const uint32_t pos = (q == 0 ? b0 : q == 1 ? b1 : q == 2 ? b2 : b3) + (rk[r] & 0x0FFFFFFFu);
-                const uint32_t p = q == 0 ? tk[0] : q == 1 ? tk[1] : q == 2 ? tk[2] : tk[3];
-                if (pos < a.pcap) a.pbuf[(uint64_t)((poff + p) * a.nsets + set) * a.pcap + pos] = e[r];
-            }
-            valid &= ~pend;
-        }
-        F2_STAMP(7);
-        return;
-    }
     for (uint32_t i = threadIdx.x; i <= np; i += kF2Threads) hist[i] = 0;
     sync_lds();
 #pragma unroll
     for (uint32_t r = 0; r < Per; ++r) {
         const uint32_t j = r * kF2Threads + threadIdx.x;
         if (j < cnt) {
-            e[r] = stage_get<Fmt>(stage, a.stage, ibase, j, pk);
+            e[r] = stage_get<Fmt>(stage, a.stage, ibase, j);
             rk[r] = atomicAdd(hist + top_bits(e[r].x, a.b1), 1u);
         }
     }
@@ -529,7 +396,7 @@ __device__ void f2_flush(const F2Args& a, uint32_t cnt, uint2* stage, uint32_t* 
 #pragma unroll
     for (uint32_t r = 0; r < Per; ++r) {
         const uint32_t j = r * kF2Threads + threadIdx.x;
-        if (j < cnt) stage_put<Fmt>(stage, a.stage, ibase, hist[top_bits(e[r].x, a.b1)] + rk[r], e[r].x, e[r].y, pk);
+        if (j < cnt) stage_put<Fmt>(stage, a.stage, ibase, hist[top_bits(e[r].x, a.b1)] + rk[r], e[r].x, e[r].y);
     }
     // wsum is free again: reuse the stage-local starts to turn reservations into deltas
     // (bucket offset of stage position j = res[p] - start[p] + j)
@@ -548,7 +415,7 @@ __device__ void f2_flush(const F2Args& a, uint32_t cnt, uint2* stage, uint32_t* 
     sync_lds();
     F2_STAMP(4);
     for (uint32_t j = threadIdx.x; j < cnt; j += kF2Threads) {
-        const uint2 x = stage_get<Fmt>(stage, a.stage, ibase, j, pk);
+        const uint2 x = stage_get<Fmt>(stage, a.stage, ibase, j);
         const uint32_t p = top_bits(x.x, a.b1);
         const uint32_t pos = hist[p] + j;
         if (pos < a.pcap) a.pbuf[(uint64_t)((poff + p) * a.nsets + set) * a.pcap + pos] = x;
@@ -560,11 +427,6 @@ __device__ void f2_flush(const F2Args& a, uint32_t cnt, uint2* stage, uint32_t* 
 // ring stays in flight): addresses past the id range are clamped into the plane
 // allocation and their words are masked by the caller's range test.
 constexpr uint32_t kRing = 8;    // S1's ring (two 512-thread workgroups per CU: 64 KB each)
-// F2's ring: 2 sub-steps = 32 KB in flight per CU.  A pure 64 MB stream by one 1024-thread
-// workgroup per CU (tools/experiments/stream_probe.hip, profiles/r03/experiments) takes
-// 13.3 us with 8 (128 KB in flight), 11.7 with 4, 11.1 with 3, 10.3 with 2: a deeper ring only
-// queues longer.  F2 at cfg 2: 21.9 us with 4, 21.3 with 3, 20.7 with 2 (round 2: 8, 24.1 us)
-constexpr uint32_t kF2Ring = 2;
 // The ring loads are buffer loads through a descriptor based at the workgroup's first id
 // (f2_rsrc): the plane pointers come from sub-partition descriptors in memory, whose address
 // space the compiler cannot infer -- plain loads through them are FLAT loads, which also count
@@ -585,47 +447,21 @@ __device__ __forceinline__ uint4 f2_load1(__amdgpu_buffer_rsrc_t rs, uint32_t lo
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
-// Modes: kF2Dense flushes the stage whenever a sub-step could overflow it (one barrier
-// per sub-step); kF2Sparse (the plan proved a block's survivors fit the stage) has no
-// barrier in the loop and flushes once at the end; kF2Seg is kF2Sparse with a flush every
-// a.seg ids (ranges longer than one stage-full: large sub-partitioned sets) -- its own
-// instantiation, because the flush inlined in the loop keeps the ring live across it (128
-// VGPRs, the whole register file at 16 waves per CU, where kF2Sparse needs 68 and leaves
-// room for the other stream's F1 / F4 waves).
-// kF2Narrow is kF2Sparse over the 6-B narrow stage (a workgroup's range < 2^16 ids).
-constexpr uint32_t kF2Dense = 0, kF2Sparse = 1, kF2Seg = 3, kF2Narrow = 4;
-
-// Src: kF2One -- one set: its descriptor from the kernel arguments, the ring through plain
-// global loads; kF2Subs -- several sub-partitions (descriptors read from memory, the ring
-// through buffer loads); kF2SubsNT -- the same with non-temporal ring loads, for sets whose w0
-// planes exceed the Infinity Cache (kNtBytes): the stream then no longer evicts the survivor
-// and target buckets F3 / F4 read next (cfg-3 shard: F2 118 -> 103 us, F3 43 -> 38, F4 19 ->
-// 17, profiles/r03/experiments/stream_nt_ab.txt).  A set the cache holds keeps cached loads:
-// non-temporal ones re-read it from HBM every call (cfg 2: F2 20.5 -> 22.9 us).
-constexpr uint32_t kF2One = 0, kF2Subs = 1, kF2SubsNT = 2;
-constexpr uint64_t kNtBytes = 192ull << 20;   // 3/4 of the 256 MB Infinity Cache
-// Win (Subs only): the sub-partitions are sorted by prefix, so a workgroup's contiguous id range
-// spans a narrow run of bitmap words, starting at its first id's: only that window (a.wwords words,
-// which the host bounded from the sub-partitions' span table) is copied to LDS, and the stage
-// takes the rest (Sparse: one final flush of up to kStageWin entries)
-template <uint32_t Mode, uint32_t Src, bool Win = false>
+// Mode: kF2Dense / kF2Sparse / kF2Seg / kF2Narrow; Src: kF2One / kF2Subs / kF2SubsNT (batch_plan.h)
+template <uint32_t Mode, uint32_t Src>
 __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
     constexpr bool Subs = Src != kF2One, NT = Src == kF2SubsNT;
     constexpr bool Narrow = Mode == kF2Narrow;
     constexpr bool Sparse = Mode == kF2Sparse || Mode == kF2Seg || Narrow;
-    constexpr bool Pack = Win && Mode == kF2Sparse;   // window + one final flush: the packed stage
-    constexpr int Fmt = Pack ? 2 : Narrow ? 1 : 0;
-    constexpr uint32_t Per = Pack ? kStagePerWin : kStagePer;
-    static_assert(!Win || (Subs && !Narrow), "window mode: sorted sub-partitions, 8-B stage");
-    extern __shared__ uint32_t sh[];   // (32 spare) | misc[8] | bm[bmw] | hist[np + 1] | wsum[17] | lost[np/32 + 1] | stage
+    constexpr int Fmt = Narrow ? 1 : 0;
+    extern __shared__ uint32_t sh[];   // (32 spare) | misc[8] | bm[nwords] | hist[np + 1] | wsum[17] | lost[np/32 + 1] | stage
     const uint32_t np = 1u << a.b1;
-    const uint32_t bmw = Win ? a.wwords : a.nwords;
     uint32_t* misc = sh + 28;
     uint32_t* bm = sh + 36;
-    uint32_t* hist = bm + bmw;
+    uint32_t* hist = bm + a.nwords;
     uint32_t* wsum = hist + np + 1;
     uint32_t* lost = wsum + 17;   // sparse mode: partitions that lost survivors past a full stage
-    uint2* stage = reinterpret_cast<uint2*>(sh + f2_fixed_words(bmw, np));
+    uint2* stage = reinterpret_cast<uint2*>(sh + f2_fixed_words(a.nwords, np));
     const uint32_t sub = Subs ? (uint32_t)a.blk_sub[blockIdx.x] : 0u;
     const SubDesc d = Subs ? a.subs[sub] : a.one;
     const uint64_t lo64 = (uint64_t)(blockIdx.x - d.blk0) * d.per_blk;
@@ -645,21 +481,7 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
     // shorten this phase either: it is the fabric, not the source); indices past the end are
     // clamped, so a clamped lane rewrites a word with its own value
     const uint32_t* bsrc = a.bitmap + sub * a.nwords;
-    // window mode: the bitmap word of the range's first (smallest) id -- the first load of the
-    // workgroup, waited for alone; the window's words (<= 2 per thread) are loaded before the ring
-    // is issued and stored to LDS after it, so their round trip overlaps the ring's
-    uint32_t wbase = 0, wv0 = 0, wv1 = 0;
-    if (Win) {
-        const uint32_t flim = min(d.lim, ((hi + 3u) & ~3u) - 4u);
-        const uint32_t f0 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(f2_rsrc(w0, lo, flim), 0, 0, 0);
-        wbase = a.Lm > 5 ? __builtin_amdgcn_readfirstlane(f0 >> (pre_off + 5)) : 0u;
-        const uint32_t i0 = wbase + threadIdx.x, i1 = i0 + kF2Threads;
-        wv0 = threadIdx.x < a.wwords && i0 < a.nwords ? bsrc[i0] : 0u;
-        wv1 = threadIdx.x + kF2Threads < a.wwords && i1 < a.nwords ? bsrc[i1] : 0u;
-    }
-    const StagePk pk{Win && a.Lm > 5 ? wbase << (pre_off + 5) : 0u, a.pk_ob};
-    if (Win) {
-    } else if ((a.nwords & 3) == 0) {
+    if ((a.nwords & 3) == 0) {
         for (uint32_t i0 = 0; i0 < a.nwords; i0 += kF2Threads * 16) {
             uint4 t[4];
             uint32_t ic[4];
@@ -685,10 +507,6 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
 #pragma unroll
     for (uint32_t r = 0; r < kF2Ring; ++r)
         ring[r] = Subs ? f2_load1<NT>(rs, lo, lo + r * kF2Sub, lim) : f2_load1g(w0, lo + r * kF2Sub, lim);
-    if (Win) {
-        if (threadIdx.x < a.wwords) bm[threadIdx.x] = wv0;
-        if (threadIdx.x + kF2Threads < a.wwords) bm[threadIdx.x + kF2Threads] = wv1;
-    }
     if (threadIdx.x < 3) misc[threadIdx.x] = 0;
     for (uint32_t i = threadIdx.x; i <= np / 32; i += kF2Threads) lost[i] = 0;
     sync_lds();
@@ -703,7 +521,7 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
         if (Mode == kF2Seg && c0 != lo && (c0 - lo) % a.seg == 0) {
             // segment boundary (block-uniform): flush while the ring's next loads are in flight
             sync_lds();
-            f2_flush<0, Per, Win>(a, misc[0] < a.stage ? misc[0] : a.stage, stage, hist, wsum, poff, 0u);
+            f2_flush<0>(a, misc[0] < a.stage ? misc[0] : a.stage, stage, hist, wsum, poff, 0u);
             if (threadIdx.x == 0) misc[0] = 0;
             sync_lds();
         }
@@ -712,7 +530,7 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
             const uint32_t sb = c0 + r * kF2Sub;
             if (sb < hi) {   // block-uniform
                 if (Mode == kF2Dense && cnt > a.stage - kF2Sub) {
-                    f2_flush<0, Per, Win>(a, cnt, stage, hist, wsum, poff, 0u);
+                    f2_flush<0>(a, cnt, stage, hist, wsum, poff, 0u);
                     cnt = 0;
                 }
                 const uint32_t j0 = sb + 4 * threadIdx.x;
@@ -726,7 +544,7 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
                 // read waited before the next issued)
                 uint32_t bw[4];
 #pragma unroll
-                for (uint32_t f = 0; f < 4; ++f) bw[f] = bm[__builtin_amdgcn_ubfe(v4[f], pre_off + 5, lm5) - wbase];
+                for (uint32_t f = 0; f < 4; ++f) bw[f] = bm[__builtin_amdgcn_ubfe(v4[f], pre_off + 5, lm5)];
 #pragma unroll
                 for (uint32_t f = 0; f < 4; ++f) {
                     // prefix bit: word pre >> 5 of the bitmap, bit pre & 31 (v_bfe masks it)
@@ -753,7 +571,7 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
                         if (sv[f]) {
                             const uint32_t at = __builtin_amdgcn_mbcnt_hi(
                                 (uint32_t)(bal[f] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[f], pos));
-                            stage_put<Fmt>(stage, a.stage, lo, at, v4[f], j0 + f, pk);
+                            stage_put<Fmt>(stage, a.stage, lo, at, v4[f], j0 + f);
                         }
                         pos += (uint32_t)__popcll(bal[f]);
                     }
@@ -768,7 +586,7 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
                             const uint32_t at = __builtin_amdgcn_mbcnt_hi(
                                 (uint32_t)(bal[f] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[f], pos));
                             if (at < a.stage) {
-                                stage_put<Fmt>(stage, a.stage, lo, at, v4[f], j0 + f, pk);
+                                stage_put<Fmt>(stage, a.stage, lo, at, v4[f], j0 + f);
                             } else {
                                 const uint32_t p = top_bits(v4[f], a.b1);
                                 atomicOr(lost + (p >> 5), 1u << (p & 31));
@@ -790,7 +608,7 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
         cnt = misc[0] < a.stage ? misc[0] : a.stage;
     }
     F2_STAMP(2);
-    if (cnt) f2_flush<Fmt, Per, Win>(a, cnt, stage, hist, wsum, poff, lo, pk);
+    if (cnt) f2_flush<Fmt>(a, cnt, stage, hist, wsum, poff, lo);
     if (Sparse) {   // partitions that lost entries: count past any stage (F3 -> fallback)
         for (uint32_t i = threadIdx.x; i <= np / 32; i += kF2Threads) {
             uint32_t m = lost[i];
@@ -817,7 +635,6 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_filter(F2Args a) {
 // for a flush (the segmented window stage flushed ~6 times per workgroup at the cfg-3 broadcast
 // rank).  A partition past its bucket capacity keeps counting (F3 sends its targets to the
 // fallback), as in the staged forms.
-constexpr uint32_t kDirParts = 4096;   // LDS counters: partitions a range may own (more: global atomics)
 
 template <uint32_t Src>
 __global__ __launch_bounds__(kF2Threads) void k_f2_direct(F2Args a) {
@@ -971,10 +788,6 @@ __device__ __forceinline__ void load_target(const uint32_t* __restrict__ tp, uin
 //      the full 160-bit key (words 1..4 read from the id planes).
 // Targets whose subtree holds fewer than min(k, n) ids go to the F4 fallback list.
 constexpr uint32_t kLaneMax = 256;   // largest subtree a lane scans alone
-
-__host__ __device__ inline uint32_t f3_words(uint32_t nsub) {
-    return (nsub + 1 + 17 + kF3Threads + 1 + 2 + 1) & ~1u;
-}
 
 // Record form (dhtgpu_batch_topk_dev with out_rec): every K6 writer of a result row -- F3's fast
 // path, the wave paths of F3 and F4 (ties, large subtrees), F4's fallback scan and its split merge
@@ -1650,8 +1463,6 @@ __global__ __launch_bounds__(kF3Threads) void k_f3_answer(F3Args a) {
 // merges the group's S lists per target (a k-way merge over the list heads, one wave per
 // target).
 constexpr uint32_t kF4Threads = scan::WAVES * 64;                 // 512
-constexpr uint32_t kFbGroup = scan::WAVES * kScanTargets;          // targets per scan role
-constexpr uint32_t kFbBlocks = 256;                                // fallback-scan workgroups
 constexpr uint32_t kFbCands = 256;                                 // merge: splits * k <= 256, splits <= 64
 constexpr uint32_t kFbSingle = 64;                                 // per-target groups up to this many listed
 
@@ -1901,265 +1712,36 @@ __global__ __launch_bounds__(kF4Threads) void k_f4(F3Args a, FbArgs f) {
     fb_list_scan<K>(a, f, cnt, blockIdx.x, lds, &last);
 }
 
-struct BatchPlan {
-    uint32_t Lm, b1, Lq, nwords, nblk1, nblk2, stage, sparse, tcap;
-    uint32_t sib;    // 1: sibling marking from the set's level-Lm cell counts (Lmin = Lm - 1)
-    uint32_t nstage; // F2's narrow stage entries (6 B each; 0: none) -- F2 then leaves room for an F3 workgroup
-    uint32_t f3cap;  // F3's LDS stage entries (kF3Cap, or the 6-sigma bound when that buys a 4th workgroup per CU)
-    uint32_t scap;   // survivors per (bucket set, partition)
-    uint32_t f3cap_wide;   // F3's LDS stage entries when F2 runs its 8-B stage (no narrow stage)
-    uint32_t cap6;         // the plan's 6-sigma partition bound (F3 stage entries, <= kF3Cap)
-    uint32_t wwords;       // F2 window mode: bitmap words in LDS per workgroup (0: the whole bitmap)
-    bool wpack;            // window mode's stage is packed (6 B; one final flush) -- else 8 B, segments
-    uint32_t nsets;        // F2 bucket sets per partition: kSets, or 1 over prefix-sorted sub-partitions
-    // variance of an F2 range's survivor count per expected survivor: ids of a range are a random
-    // sample (1 - f), or -- prefix-sorted sub-partitions -- whole level-Lm cells of mu ids each,
-    // marked with probability f ((1 - f) mu + 1: ~30x the binomial at the cfg-3 shard)
-    double clump;
-    bool fits;   // partitions' survivors fit the F3 stage on uniform ids
-    uint64_t per_blk;
-};
-
-
-
-uint32_t floor_log2(uint64_t x) {
-    uint32_t r = 0;
-    while (x > 1) { x >>= 1; ++r; }
-    return r;
-}
-
-// P(X < k) for X ~ Poisson(m)
-double poisson_below(double m, uint32_t k) {
-    double term = std::exp(-m), sum = 0.0;
-    for (uint32_t j = 0; j < k; ++j) {
-        sum += term;
-        term *= m / (double)(j + 1);
-    }
-    return sum;
-}
-
-BatchPlan plan_batch_compute(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t pf, uint32_t wwords);
-
-// plan_batch is a pure function of (n, q, k, CUs, plan flags, window), asked three times per call
-// (workspace size, clean head, the launch): the last few plans are kept per host thread
-BatchPlan plan_batch(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t pf = 0, uint32_t wwords = 0) {
-    struct Entry { uint64_t n; uint32_t q, k; int cus; uint32_t pf; uint32_t ww; BatchPlan P; bool used; };
-    thread_local Entry cache[6] = {};
-    thread_local uint32_t next = 0;
-    for (const Entry& e : cache)
-        if (e.used && e.n == n && e.q == q && e.k == k && e.cus == num_cus && e.pf == pf && e.ww == wwords)
-            return e.P;
-    Entry& e = cache[next++ % 6u];
-    e = Entry{n, q, k, num_cus, pf, wwords, plan_batch_compute(n, q, k, num_cus, pf, wwords), true};
-    return e.P;
-}
-
-BatchPlan plan_batch_compute(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t pf, uint32_t wwords) {
-    BatchPlan P;
-    const bool cells = (pf & kPlanCells) != 0, sorted = (pf & kPlanSorted) != 0;
-    P.wwords = wwords;
-    // mark level: 4k or more ids per level-Lm subtree -- or one level finer (2k..4k) when, on
-    // uniform ids, fewer than 0.01 of the q targets are expected to land in a subtree with
-    // under k ids (those go to the F4 brute force).  Without the finer step a prefix shard
-    // just under a power of two (n = 2^24 - few) would mark at half the resolution and
-    // double the survivors.
-    const uint64_t per = 4ull * k;
-    P.Lm = n >= per ? floor_log2(n / per) : 0;
-    P.sib = 0;
-    if (n >= per && P.Lm < kMaxLm) {
-        if (poisson_below((double)n / (double)(1ull << (P.Lm + 1)), k) * q <= 0.01) {
-            ++P.Lm;
-        } else if (cells && P.Lm + 1 == kMaxLm && poisson_below((double)n / (double)(1ull << P.Lm), k) * q <= 0.01) {
-            // sibling marking (the set's level-kMaxLm cell counts, kept with its sub-partitions):
-            // a target whose level-Lm cell holds < k ids marks the sibling cell too, so it answers
-            // from its complete level-(Lm - 1) subtree; only a short PAIR falls back.  One level
-            // finer than the rule above allows: the survivors drop from 1 - exp(-q / 2^(Lm-1)) to
-            // about 1 - exp(-q / 2^Lm) (cfg 3's broadcast rank: 39 % -> 22 %)
-            ++P.Lm;
-            P.sib = 1;
-        }
-    }
-    if (P.Lm > kMaxLm) P.Lm = kMaxLm;
-    // survivors on uniform ids: n (1 - exp(-q (1 + p) / 2^Lm)), p = the fraction of targets that
-    // mark a sibling too; partitions of about kF3Cap / 2
-    const double psib = P.sib ? poisson_below((double)n / (double)(1ull << P.Lm), k) : 0.0;
-    const double f = 1.0 - std::exp(-(double)q * (1.0 + psib) / (double)(1ull << P.Lm));
-    const double surv = (double)n * f + 1.0;
-    uint32_t b1 = 0;
-    while (b1 + P.sib < P.Lm && surv / (double)(1ull << b1) > kF3Cap / 2) ++b1;   // F3 sorts level Lm - sib
-    if (P.Lm > kMaxSubBits && b1 < P.Lm - kMaxSubBits) b1 = P.Lm - kMaxSubBits;
-    if (b1 > 13) b1 = 13;   // kMaxParts
-    // a partition's survivors come in whole level-Lm subtrees (n / 2^Lm ids each, marked
-    // with probability f): on uniform ids mean s f mu, variance s f (1 - f) mu^2 + s f mu
-    // over its s = 2^(Lm - b1) subtrees.  Split further until mean + 6 sigma fits the F3
-    // stage (an overflowing partition sends its targets to the brute force); plans that
-    // cannot are refused (batch_supported), e.g. n >> 2^24 with its 256-id subtrees.
-    P.fits = false;
-    double need = (double)kF3Cap;   // the partition bound the plan was accepted with
-    for (;; ++b1) {
-        const double sub = (double)(1ull << (P.Lm - b1)), mu = (double)n / (double)(1ull << P.Lm);
-        const double mean = sub * f * mu, var = sub * f * (1.0 - f) * mu * mu + sub * f * mu;
-        need = mean + 6.0 * std::sqrt(var) + 64.0;
-        if (need <= (double)kF3Cap) { P.fits = true; break; }
-        if (b1 >= 13 || b1 + P.sib >= P.Lm) break;
-    }
-    P.b1 = b1;
-    // prefix-sorted sub-partitions (the plans with cell counts): an F2 workgroup's range is a
-    // narrow prefix range, so a partition's survivors come from one or two workgroups -- one
-    // bucket set, sized for the whole partition (with 8 sets planned for an eighth each, every
-    // partition overflowed its set)
-    P.nsets = sorted ? 1u : kSets;
-    P.clump = sorted ? (1.0 - f) * (double)n / (double)(1ull << P.Lm) + 1.0 : 1.0 - f;
-    {   // a set holds each id with probability 1 / kSets (ids are spread over the blocks by
-        // index, independently of their prefix): mean + 8 sigma + 64 of one set's share
-        const double sub = (double)(1ull << (P.Lm - b1)), mu = (double)n / (double)(1ull << P.Lm) / P.nsets;
-        const double mean = sub * f * mu, var = sub * f * (1.0 - f) * mu * mu + sub * f * mu;
-        const double cap = mean + 8.0 * std::sqrt(var) + 64.0;
-        P.scap = cap >= (double)kF3Cap ? kF3Cap : ((uint32_t)cap + 63u) & ~63u;
-        // F3 gathers exactly after the counts: the survivors' bytes only (PMC at cfg 2: 18.5 MB
-        // against 19.7 MB algorithmic; round 2's fixed speculative slots fetched 40 MB) and no
-        // slower (cfg-2 step 37.7-38.1 us against 38.3-38.4 with a planned mean + 5 sigma)
-    }
-    // F3 sorts by up to 1 bit below the mark level (finer candidate ranges), <= 4096 bins
-    P.Lq = P.Lm + 1 < 32 ? P.Lm + 1 : 32;
-    while (P.Lq > P.Lm && P.Lq - P.b1 > 12) --P.Lq;
-    // F3's LDS: four workgroups per CU (40 KB each) where the plan allows -- sort one bit less
-    // finely, and stage the plan's own 6-sigma bound instead of kF3Cap entries (a partition past
-    // it sends its targets to the exact fallback, as one past kF3Cap always did).  The cfg-3
-    // shard's plan (b1 = 8, 4096 sort bins: 52 KB) ran three per CU, 2.7 rounds of 2,048 blocks.
-    P.f3cap = kF3Cap;
-    auto lds3 = [&](uint32_t Lq, uint32_t cap) {
-        return (size_t)f3_words(1u << (Lq - P.b1)) * 4 + (size_t)(cap + kF3Threads) * 8;
-    };
-    constexpr size_t kF3Lds4 = kLdsMax / 4;
-    const uint32_t cap6 = std::min<uint32_t>(kF3Cap, ((uint32_t)need + 63u) & ~63u);
-    P.cap6 = cap6;
-    if (P.fits && lds3(P.Lq, P.f3cap) > kF3Lds4) {
-        for (uint32_t lq = P.Lq; lq >= P.Lm && lq > P.b1; --lq) {
-            if (lds3(lq, kF3Cap) <= kF3Lds4) { P.Lq = lq; break; }
-            if (lds3(lq, cap6) <= kF3Lds4) { P.Lq = lq; P.f3cap = cap6; break; }
-            if (lq == P.Lm) break;
-        }
-    }
-    P.nwords = P.Lm >= 5 ? (1u << (P.Lm - 5)) : 1u;
-    P.nblk1 = (q + kF1Threads - 1) / kF1Threads;
-    // target buckets: mean + 6 sigma + 64 (uniform targets); overflow spills to F4
-    const double mu = (double)q / (double)(1u << P.b1);
-    P.tcap = ((uint32_t)(mu + 6.0 * std::sqrt(mu) + 64.0) + 63u) & ~63u;
-    // F2: one persistent workgroup per CU, ranges in whole chunks
-    const uint64_t chunks = (n + kF2Step - 1) / kF2Step;
-    const uint64_t g = num_cus > 0 ? (uint64_t)num_cus : 256;
-    const uint64_t cpb = (chunks + g - 1) / g;
-    P.per_blk = (cpb ? cpb : 1) * kF2Step;
-    P.nblk2 = (uint32_t)((n + P.per_blk - 1) / P.per_blk);
-    // F2 LDS stage: what is left of the LDS next to the bitmap (or its window) and histogram
-    const size_t fixed = (size_t)f2_fixed_words(wwords ? wwords : P.nwords, 1u << P.b1) * 4;
-    // (window mode: a packed 6-B stage while one final flush holds the range's survivors)
-    const size_t room = fixed < kLdsMax ? (kLdsMax - fixed) / 8 : 0;
-    const size_t room6 = fixed + 1024 < kLdsMax ? (kLdsMax - fixed - 1024) / 6 : 0;
-    P.stage = wwords ? (uint32_t)std::min<size_t>(room6, kStageWin) : (uint32_t)(room < kStage ? room : kStage);
-    P.wpack = wwords != 0;
-    // sparse mode when a block's survivors (mean + 8 sigma on uniform ids) fit the stage,
-    // with ranges shrunk (more blocks) while that helps
-    P.sparse = 0;
-    for (uint64_t pb = P.per_blk; pb >= kF2Step; pb /= 2) {
-        const double mean = (double)pb * f, sd = std::sqrt(mean * P.clump);
-        if (mean + 8.0 * sd + 256.0 <= (double)P.stage) {
-            P.sparse = 1;
-            P.per_blk = (pb / kF2Step) * kF2Step;
-            P.nblk2 = (uint32_t)((n + P.per_blk - 1) / P.per_blk);
-            break;
-        }
-        if (pb == kF2Step) break;
-    }
-    // window mode past one stage-full: the segmented instantiation's flush holds kStagePer entries
-    // per thread in registers (its ring stays live across the flush: 128 VGPRs at most)
-    if (wwords && !P.sparse) {
-        P.stage = (uint32_t)(room < kStage ? room : kStage);
-        P.wpack = false;
-    }
-    // F2's narrow stage (6 B per entry: ranges < 2^16 ids, the cfg-2 shape): sized so that F2
-    // plus one F3 workgroup fit a CU's LDS -- the F2 of one batch in flight and the F3 of another
-    // then share CUs instead of waiting for each other's workgroups to drain.  F3 stages its
-    // plan's own 6-sigma bound where that is what makes the pair fit (a partition past it sends
-    // its targets to the exact fallback, as one past kF3Cap does).  1 KB of margin per kernel
-    // for the LDS allocation granule.
-    P.nstage = 0;
-    P.f3cap_wide = P.f3cap;
-    if (P.sparse && P.per_blk <= 65536 && !wwords) {
-        const double mean = (double)P.per_blk * f, sd = std::sqrt(mean * (1.0 - f));
-        const double need2 = mean + 8.0 * sd + 256.0;
-        for (int pass = 0; pass < 2 && !P.nstage; ++pass) {
-            uint32_t cap3 = P.f3cap_wide;   // pass 1: F3 stages the 6-sigma bound to make room
-            if (pass == 1) {
-                if (!P.fits || cap6 >= cap3) break;
-                cap3 = cap6;
-            }
-            const size_t f3l = (lds3(P.Lq, cap3) + 1023) & ~(size_t)1023;
-            if (fixed + f3l + 1024 >= kLdsMax) continue;
-            const size_t room6 = (kLdsMax - f3l - fixed - 1024) / 6;
-            if ((double)room6 >= need2) {
-                P.nstage = (uint32_t)std::min<size_t>(room6, kStage) & ~1u;
-                P.f3cap = cap3;   // committed only with the narrow stage it makes room for
-            }
-        }
-    }
-    return P;
-}
-
-size_t f2_lds(const BatchPlan& P, bool narrow = false) {
-    const size_t fixed = (size_t)f2_fixed_words(P.wwords ? P.wwords : P.nwords, 1u << P.b1) * 4;
-    if (P.wpack) return fixed + (size_t)P.stage * 6;   // window mode's packed stage
-    return fixed + (narrow ? (size_t)P.nstage * 6 : (size_t)P.stage * 8);
-}
-
-size_t f3_lds(const BatchPlan& P, uint32_t cap) {
-    const uint32_t nsub = 1u << (P.Lq - P.b1);
-    return (size_t)f3_words(nsub) * 4 + (size_t)(cap + kF3Threads) * 8;
-}
-
 // DHTGPU_DBG=256: per-block phase profiles of F2 and F3 from their s_memrealtime stamps
 // (100 MHz real-time counter: 10 ns ticks), printed to stderr (synchronises s)
-void print_phase_profile(const BatchPlan& P, uint32_t nblk2, uint32_t np, unsigned long long* stamps, hipStream_t s) {
+void print_phase_profile(uint32_t nblk2, uint32_t np, unsigned long long* stamps, hipStream_t s) {
     if (!stamps) return;
-    const uint32_t dbg = 256;
-    if (dbg & 256) {   // phase profile of F2 (100 MHz real-time stamps: 10 ns ticks)
+    auto pct = [](std::vector<double> d) {
+        std::sort(d.begin(), d.end());
+        const size_t m = d.size();
+        char buf[96];
+        snprintf(buf, sizeof buf, "p10 %.2f p50 %.2f p90 %.2f max %.2f", d[m / 10], d[m / 2], d[m * 9 / 10], d[m - 1]);
+        return std::string(buf);
+    };
+    {   // phase profile of F2 (100 MHz real-time stamps: 10 ns ticks)
         std::vector<unsigned long long> h((size_t)nblk2 * 16);
         (void)hipMemcpyAsync(h.data(), stamps + 8192 * 16, h.size() * 8, hipMemcpyDeviceToHost, s);
         (void)hipStreamSynchronize(s);
         unsigned long long t0 = ~0ull;
         for (uint32_t b = 0; b < nblk2; ++b) t0 = h[b * 16] && h[b * 16] < t0 ? h[b * 16] : t0;
-        auto pct2 = [](std::vector<double> d) {
-            std::sort(d.begin(), d.end());
-            const size_t m = d.size();
-            char buf[96];
-            snprintf(buf, sizeof buf, "p10 %.2f p50 %.2f p90 %.2f max %.2f", d[m / 10], d[m / 2], d[m * 9 / 10], d[m - 1]);
-            return std::string(buf);
-        };
         const char* nm[] = {"", "bitmap+ring", "stream+filter", "flush hist", "flush reserve+scan", "flush writes"};
         for (int i = 1; i <= 5; ++i) {
             std::vector<double> d;
             for (uint32_t b = 0; b < nblk2; ++b)
                 if (h[b * 16 + 5]) d.push_back((double)(h[b * 16 + i] - h[b * 16 + i - 1]) / 100.0);
-            if (!d.empty()) fprintf(stderr, "  F2 %-20s %s\n", nm[i], pct2(d).c_str());
-        }
-        {   // window flushes (the last one's sub-phases): ranks in registers, table, offsets; spill flag
-            const char* nw[] = {"win load", "win reserve+write"};
-            const int from[] = {2, 6}, to[] = {6, 7};
-            for (int i = 0; i < 2; ++i) {
-                std::vector<double> d;
-                for (uint32_t b = 0; b < nblk2; ++b)
-                    if (h[b * 16 + 5] && h[b * 16 + to[i]] > h[b * 16 + from[i]])
-                        d.push_back((double)(h[b * 16 + to[i]] - h[b * 16 + from[i]]) / 100.0);
-                if (!d.empty()) fprintf(stderr, "  F2 %-20s %s\n", nw[i], pct2(d).c_str());
-            }
+            if (!d.empty()) fprintf(stderr, "  F2 %-20s %s\n", nm[i], pct(d).c_str());
         }
         std::vector<double> st, en;
         for (uint32_t b = 0; b < nblk2; ++b)
             if (h[b * 16 + 5]) { st.push_back((double)(h[b * 16] - t0) / 100.0); en.push_back((double)(h[b * 16 + 5] - t0) / 100.0); }
-        if (!st.empty()) fprintf(stderr, "  F2 start %s\n  F2 end   %s\n", pct2(st).c_str(), pct2(en).c_str());
+        if (!st.empty()) fprintf(stderr, "  F2 start %s\n  F2 end   %s\n", pct(st).c_str(), pct(en).c_str());
     }
-    if (dbg & 256) {   // phase profile of F3 (100 MHz real-time stamps: 10 ns ticks)
+    {   // phase profile of F3 (100 MHz real-time stamps: 10 ns ticks)
         std::vector<unsigned long long> h((size_t)np * 16);
         (void)hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, s);
         (void)hipStreamSynchronize(s);
@@ -2169,13 +1751,6 @@ void print_phase_profile(const BatchPlan& P, uint32_t nblk2, uint32_t np, unsign
         for (uint32_t b = 0; b < np; ++b)
             if (h[b * 16 + 7]) live.push_back(b);
         const size_t nb = live.size();
-        auto pct = [](std::vector<double> d) {
-            std::sort(d.begin(), d.end());
-            const size_t m = d.size();
-            char buf[96];
-            snprintf(buf, sizeof buf, "p10 %.2f p50 %.2f p90 %.2f max %.2f", d[m / 10], d[m / 2], d[m * 9 / 10], d[m - 1]);
-            return std::string(buf);
-        };
         if (nb) {
             for (int i = 1; i < 8; ++i) {
                 std::vector<double> d;
@@ -2243,8 +1818,6 @@ void set_lds_attributes() {
                         (const void*)k_f2_filter<kF2Dense, kF2SubsNT>, (const void*)k_f2_filter<kF2Sparse, kF2SubsNT>,
                         (const void*)k_f2_filter<kF2Seg, kF2SubsNT>,
                         (const void*)k_f2_filter<kF2Narrow, kF2SubsNT>,
-                        (const void*)k_f2_filter<kF2Sparse, kF2Subs, true>, (const void*)k_f2_filter<kF2Seg, kF2Subs, true>,
-                        (const void*)k_f2_filter<kF2Sparse, kF2SubsNT, true>, (const void*)k_f2_filter<kF2Seg, kF2SubsNT, true>,
                         (const void*)k_f3_answer<8, false, true, false>,  (const void*)k_f3_answer<16, false, true, false>,
                         (const void*)k_f3_answer<32, false, true, false>, (const void*)k_f3_answer<8, true, true, false>,
                         (const void*)k_f3_answer<16, true, true, false>,  (const void*)k_f3_answer<32, true, true, false>,
@@ -2257,188 +1830,7 @@ void set_lds_attributes() {
     for (const void* f : fs) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
 }
 
-// workspace: bitmap[nsub][nwords] | ctr[64] | pcount[kSets][NP] | tcount[kMaxParts * kCtrStride] |
-// tie_hdr[NP * kTieSlots] | fb done[kFbBlocks] | tie_cnt[NP] -- all-zero between calls -- |
-// fb_list[q] | tspill[q] | pstat[NP] | tbuf[NP * tcap] | tie_cand[NP * kTieSlots * 64] |
-// pbuf[NP * kSets * scap] | fb rec[kFbBlocks * kFbGroup * k * 6] | sub descriptors | F2 map
-// (NP = nsub * np partitions over all sub-partitions)
-constexpr uint32_t kMaxParts = 1u << 15;
-constexpr uint32_t kMaxSubs = 256;            // F2's workgroup -> sub-partition map is u8
-constexpr uint32_t kMaxF2Blocks = 65536;
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
-
-struct WsLayout {
-    size_t ctr, bitmap, pcount, tcount, tie_hdr, fb_done, tie_cnt, ccount, clean;
-    size_t fb_list, fb_sub, tspill, pstat, tbuf, tie_cand, pbuf, fb_rec, desc, blk_sub, cbuf, total;
-};
-
-// F1's two-pass form (k_f1_coarse + k_f1_fine) for batches of >= kF1CoarseMinQ targets: the
-// coarse bins are the finest split (<= b1 and Lm - 5 bits per sub-partition) that keeps >= 512
-// targets per bin and >= 16 per (F1a workgroup, bin) -- each reservation a run of >= 128 B (2,048
-// bins at 2^20 targets left 2 per run: F1a 34 us, 524 K reservations) -- with F1b's LDS within
-// kF1bLdsWords.  c = ~0u: one pass.
-struct F1Coarse { uint32_t c, nbins, ccap; };
-F1Coarse f1_coarse(const BatchPlan& P, uint32_t nsub, uint32_t q) {
-    F1Coarse f{~0u, 0, 0};
-    if (q < kF1CoarseMinQ || P.Lm < 5) return f;
-    auto lds_ok = [&](uint32_t c) { return (1u << (P.Lm - c - 5)) + (1u << (P.b1 - c)) <= kF1bLdsWords; };
-    uint32_t c = 0;
-    while (c < P.b1 && c + 5 < P.Lm && ((uint64_t)nsub << (c + 1)) <= kF1aTargets / 16 &&
-           ((uint64_t)nsub << (c + 1)) * 512 <= q)
-        ++c;
-    while (c < P.b1 && c + 5 < P.Lm && !lds_ok(c)) ++c;
-    if (!lds_ok(c) || ((uint64_t)nsub << c) > kMaxCoarse) return f;
-    f.c = c;
-    f.nbins = nsub << c;
-    const double M = (double)q / (double)f.nbins;
-    f.ccap = ((uint32_t)(M + 8.0 * std::sqrt(M) + 64.0) + 63u) & ~63u;
-    return f;
-}
-
-WsLayout ws_layout(const BatchPlan& P, uint32_t nsub, uint32_t q, uint32_t k) {
-    const size_t NP = (size_t)nsub << P.b1;
-    WsLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = off;
-        off += al256(bytes);
-        return r;
-    };
-    // bitmap first and the counter arrays sized for kMaxParts partitions: the compact layout
-    // (counters right behind one another) cost F1 0.5 us and the pipelined cfg-2 step 0.3 us
-    // (measured); the clean head is memset once per workspace
-    L.bitmap = take(std::max<size_t>(65536, (size_t)nsub * P.nwords * 4));
-    L.ctr = take(256);
-    L.pcount = take((size_t)kSets * NP * 4);
-    L.tcount = take((size_t)kMaxParts * kCtrStride * 4);
-    L.tie_hdr = take((size_t)kMaxParts * kTieSlots * 16);
-    L.fb_done = take((size_t)kFbBlocks * 4);
-    L.tie_cnt = take((size_t)kMaxParts * 4);
-    L.ccount = take((size_t)kMaxCoarse * 4);
-    L.clean = off;
-    L.fb_list = take((size_t)q * 4);
-    L.fb_sub = take((size_t)q);
-    L.tspill = take((size_t)q * 4);
-    L.pstat = take(NP * 4);
-    L.tbuf = take(NP * P.tcap * 8);
-    L.tie_cand = take(NP * kTieSlots * 64 * 8);
-    L.pbuf = take(NP * P.nsets * P.scap * 8);
-    L.fb_rec = take((size_t)kFbBlocks * kFbGroup * k * 24);
-    L.desc = take((size_t)kMaxSubs * sizeof(SubDesc));
-    L.blk_sub = take(kMaxF2Blocks);
-    const F1Coarse fc = f1_coarse(P, nsub, q);
-    L.cbuf = take((size_t)fc.nbins * fc.ccap * 8);
-    L.total = off;
-    return L;
-}
-
-// F2's workgroups over the sub-partitions: whole rounds of num_cus workgroups, each
-// sub-partition's share in proportion to its ids.  Sparse mode: the stage is flushed every
-// *seg ids, the most it holds on uniform ids (mean + 8 sigma + 256 survivors) in whole ring
-// turns -- one round of workgroups however large the set; when not even one ring turn fits, no
-// workgroup gets more ids than that bound.
-uint32_t deal_f2_blocks(const BatchPlan& P, const SubSpec* subs, uint32_t nsub, uint32_t q_plan, int num_cus,
-                        SubDesc* d, uint32_t* seg) {
-    const double f = 1.0 - std::exp(-(double)q_plan / (double)(1ull << P.Lm));
-    uint64_t pb_cap = 1ull << 40;   // dense mode: no cap
-    if (P.sparse) {
-        pb_cap = kF2Step;
-        for (uint64_t pb = kF2Step; pb <= (1ull << 31); pb += kF2Step) {
-            const double mean = (double)pb * f, sd = std::sqrt(mean * P.clump);
-            if (mean + 8.0 * sd + 256.0 > (double)P.stage) break;
-            pb_cap = pb;
-        }
-    }
-    *seg = 0xFFFFFFFFu;
-    constexpr uint64_t turn = (uint64_t)kF2Ring * kF2Sub;
-    if (P.sparse && pb_cap >= turn) {
-        *seg = (uint32_t)std::min<uint64_t>(pb_cap / turn * turn, 0x80000000ull);
-        pb_cap = 1ull << 40;
-    }
-    const uint64_t g = num_cus > 0 ? (uint64_t)num_cus : 256;
-    uint64_t n_tot = 0, need = 0;
-    for (uint32_t i = 0; i < nsub; ++i) {
-        n_tot += subs[i].n;
-        need += (subs[i].n + pb_cap - 1) / pb_cap;
-    }
-    const uint64_t total = std::max<uint64_t>(1, (need + g - 1) / g) * g;
-    uint32_t blk = 0;
-    for (uint32_t i = 0; i < nsub; ++i) {
-        const uint64_t n = subs[i].n;
-        uint64_t want = n_tot ? (uint64_t)std::llround((double)total * (double)n / (double)n_tot) : 0;
-        want = std::max<uint64_t>(want, (n + pb_cap - 1) / pb_cap);
-        if (n && !want) want = 1;
-        // whole groups of kSets workgroups: block b writes bucket set b % kSets, and scap plans
-        // every set for 1 / kSets of a partition's survivors (a sub-partition dealt 4 workgroups
-        // would fill only 4 sets, each twice over: overflowing partitions, fallback scans)
-        want = (want + kSets - 1) / kSets * kSets;
-        uint64_t per = want ? (n + want - 1) / want : kF2Step;
-        per = (per + kF2Step - 1) / kF2Step * kF2Step;
-        if (per > pb_cap) per = pb_cap;
-        const uint64_t nb = n ? (n + per - 1) / per : 0;
-        const uint64_t lim = (subs[i].w0s ? subs[i].stride : 5 * subs[i].stride) - 4;
-        d[i] = SubDesc{subs[i].w0s ? subs[i].w0s : subs[i].planes, subs[i].planes, subs[i].stride, n, subs[i].gidx,
-                       subs[i].base, (uint32_t)(lim < 0xFFFFFFF0ull ? lim : 0xFFFFFFF0ull), blk, (uint32_t)nb, per};
-        blk += (uint32_t)nb;
-    }
-    return blk;
-}
-
-// What a launch does with its plan once F2's workgroups are dealt (launch_batch_topk; the plan
-// query dhtgpu_batch_plan reports the same values): whether some workgroup's range spans more
-// than one segment, whether F2 runs the narrow stage, F2's mode among the stage-sorting
-// instantiations (window and direct forms are chosen by the caller), the stage entries F2 and
-// F3 are given, and whether F1 runs as coarse + fine.
-struct BatchRoute {
-    bool seg_used, narrow, f1_two_pass;
-    uint32_t f2_mode, f2_stage, f3_cap;
-    F1Coarse f1c;
-};
-BatchRoute route_batch(const BatchPlan& P, const BatchPlan& P0, const SubDesc* hd, uint32_t nsub, uint32_t seg,
-                       bool direct, uint32_t q, uint32_t q_plan) {
-    BatchRoute R{};
-    for (uint32_t i = 0; i < nsub; ++i) R.seg_used = R.seg_used || (hd[i].nblk && hd[i].per_blk > seg);
-    // the narrow stage: every workgroup's range under 2^16 ids and its survivors (mean + 8 sigma
-    // + 256 on uniform ids) within the narrow stage; no segments
-    R.narrow = !direct && P.nstage && P.sparse && !R.seg_used;
-    {
-        const double f = 1.0 - std::exp(-(double)q_plan / (double)(1ull << P.Lm));
-        for (uint32_t i = 0; i < nsub && R.narrow; ++i) {
-            const double mean = (double)hd[i].per_blk * f, sd = std::sqrt(mean * P.clump);
-            if (hd[i].nblk && (hd[i].per_blk > 65536 || mean + 8.0 * sd + 256.0 > (double)P.nstage)) R.narrow = false;
-        }
-    }
-    R.f2_mode = R.narrow ? kF2Narrow : P.sparse && R.seg_used ? kF2Seg : P.sparse ? kF2Sparse : kF2Dense;
-    R.f2_stage = R.narrow ? P.nstage : P.stage;
-    R.f3_cap = R.narrow ? P.f3cap : P.f3cap_wide;
-    R.f1c = f1_coarse(P0, nsub, q);
-    R.f1_two_pass = R.f1c.nbins && P.Lm == P0.Lm && P.b1 == P0.b1;
-    return R;
-}
-
 }  // namespace
-
-bool batch_supported(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t nsub, uint32_t pf) {
-    if (k == 0 || k > DHTGPU_MAX_K_DEV || n >= (1ull << 31) || nsub == 0 || nsub > kMaxSubs) return false;
-    const BatchPlan P = plan_batch(n, q, k, num_cus, pf);
-    if ((uint64_t)q * nsub > kMaxQ) return false;
-    if (((uint64_t)nsub << P.b1) > kMaxParts) return false;
-    // dense mode flushes whenever less than one sub-step of room is left
-    if (!P.fits || P.Lm - P.b1 > 13 || (!P.sparse && P.stage < kF2Sub + 1024)) return false;
-    return f3_lds(P, P.f3cap_wide) <= kLdsMax && f2_lds(P) <= kLdsMax;
-}
-
-size_t batch_ctr_offset(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub, uint32_t pf) {
-    return ws_layout(plan_batch(n, q_plan, k, num_cus, pf), nsub, 0, k).ctr;
-}
-
-size_t batch_clean_bytes(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub, uint32_t pf) {
-    return ws_layout(plan_batch(n, q_plan, k, num_cus, pf), nsub, 0, k).clean;
-}
-
-size_t batch_bytes(uint64_t n, uint32_t q, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub, uint32_t pf) {
-    return ws_layout(plan_batch(n, q_plan, k, num_cus, pf), nsub, q, k).total;
-}
 
 hipError_t batch_read_stats(const void* ws, uint64_t n, uint32_t q, uint32_t q_plan, uint32_t k, int num_cus,
                             uint32_t* stats4, hipStream_t s, uint32_t nsub, uint32_t pf) {
@@ -2599,22 +1991,19 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
         if (e != hipSuccess) return e;
     }
     const uint32_t q = c.q, k = c.k;
-    // the sub-partitions (a set that needs no split is its own one sub-partition); the plan is
-    // the largest one's
+    // the sub-partitions (a set that needs no split is its own one sub-partition)
     const SubSpec one{c.planes, c.w0s, c.stride, c.n, c.gidx, c.base};
-    const SubSpec* subs = c.nsub ? c.subs : &one;
     const uint32_t nsub = c.nsub ? c.nsub : 1u;
-    uint64_t n_max = 0, n_all = 0;
-    for (uint32_t i = 0; i < nsub; ++i) {
-        n_max = std::max<uint64_t>(n_max, subs[i].n);
-        n_all += subs[i].n;
-    }
-    const bool nt = 4 * n_all > kNtBytes;   // F2's ring: non-temporal past the Infinity Cache
-    const uint32_t pf = (c.cells ? kPlanCells : 0u) | (c.sorted ? kPlanSorted : 0u);
-    BatchPlan P = plan_batch(n_max, c.q_plan, k, c.num_cus, pf);
-    const BatchPlan P0 = P;   // the workspace layout's plan (window mode may refine P below)
-    const uint32_t np = 1u << P.b1, NP = nsub * np;
-    uint32_t dbg = c.dbg & 256u;   // the only diagnostics bit: phase stamps (results unchanged)
+    // everything the launch decides (batch_plan.cpp); the only diagnostics bit is the phase stamps
+    SubDesc hd[kMaxSubs];
+    BatchDecision D;
+    const BatchShape shape{c.nsub ? c.subs : &one, nsub, q, c.q_plan, k, c.num_cus,
+                           (c.cells ? kPlanCells : 0u) | (c.sorted ? kPlanSorted : 0u), c.spans, c.n, c.dbg & 256u,
+                           c.fb_hint && *c.fb_hint == 0u};
+    if (!decide_batch(shape, hd, &D)) return hipErrorInvalidValue;
+    const BatchPlan& P = D.P;
+    const BatchRoute& R = D.R;
+    const uint32_t np = 1u << P.b1, NP = nsub * np, nblk2 = D.nblk2, dbg = D.dbg;
     hipEvent_t* ev = c.ev;
     const WsLayout Ly = ws_layout(P, nsub, q, k);
     uint8_t* const w = static_cast<uint8_t*>(c.ws);
@@ -2638,85 +2027,6 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
     // sub-partition descriptors and F2's workgroup map: one sub-partition travels in the kernel
     // arguments; several are uploaded when they differ from what this workspace holds
     // (steady-state calls upload nothing)
-    SubDesc hd[kMaxSubs];
-    uint32_t seg = 0, pk_ob = 0;
-    uint32_t nblk2 = deal_f2_blocks(P, subs, nsub, c.q_plan, c.num_cus, hd, &seg);
-    // window mode (prefix-sorted sub-partitions with span tables): every workgroup's bitmap window
-    // is bounded by its sub-partition's largest cell span over as many consecutive ids as the
-    // workgroup holds; taken when that bound is small (the cfg-3 shard: ~520 words of 16,384)
-    bool direct = false;   // k_f2_direct (sorted sub-partitions: no stage)
-    if (c.spans && c.sorted && nsub > 1 && P.Lm >= 6 && P.Lm <= kMaxLm) {
-        auto need = [&](const SubDesc* dd) {
-            uint32_t w = 0;
-            for (uint32_t i = 0; i < nsub; ++i) {
-                if (!dd[i].nblk) continue;
-                uint32_t j = 0;
-                while (j < 31 && (1ull << j) < dd[i].per_blk) ++j;
-                const uint32_t span19 = c.spans[i * 32 + j];   // level-kMaxLm cells
-                w = std::max<uint32_t>(w, (span19 >> (kMaxLm - P.Lm + 5)) + 3u);
-            }
-            return w;
-        };
-        if (P.nsets == 1) {   // direct: one persistent workgroup per CU (no stage bounds a range)
-            BatchPlan Pd = P;
-            Pd.sparse = 0;
-            SubDesc hw[kMaxSubs];
-            uint32_t segw = 0;
-            const uint32_t nbw = deal_f2_blocks(Pd, subs, nsub, c.q_plan, c.num_cus, hw, &segw);
-            uint32_t wd = 64;
-            while (wd < need(hw)) wd <<= 1;
-            if (wd <= 2 * kF2Threads && 2 * wd <= P.nwords && nbw <= kMaxF2Blocks) {
-                direct = true;
-                P.wwords = wd;
-                nblk2 = nbw;
-                std::copy(hw, hw + nsub, hd);
-            }
-        }
-        uint32_t ww = 64;
-        while (ww < need(hd)) ww <<= 1;
-        if (!direct && P.sparse && ww <= 2 * kF2Threads && 2 * ww <= P.nwords) {
-            BatchPlan Pw = plan_batch(n_max, c.q_plan, k, c.num_cus, pf, ww);
-            SubDesc hw[kMaxSubs];
-            uint32_t segw = 0;
-            uint32_t nbw = deal_f2_blocks(Pw, subs, nsub, c.q_plan, c.num_cus, hw, &segw);
-            bool segd = false;
-            for (uint32_t i = 0; i < nsub; ++i) segd = segd || (hw[i].nblk && hw[i].per_blk > segw);
-            // ranges past one packed stage-full: 8-B segments (kStagePer entries in registers) in the
-            // LDS the window leaves.  (Sizing the segmented stage so that two F3 workgroups of the
-            // other call in flight fit beside F2 measured equal at the cfg-3 prefix rank, 0.148 ms
-            // both, and slower at the broadcast rank, 0.558 -> 0.593 ms: profiles/r06/window_ab.txt)
-            if (Pw.sparse && segd) {
-                const size_t fx = (size_t)f2_fixed_words(ww, 1u << Pw.b1) * 4;
-                Pw.stage = (uint32_t)std::min<size_t>(fx < kLdsMax ? (kLdsMax - fx) / 8 : 0, kStage);
-                Pw.wpack = false;
-                nbw = deal_f2_blocks(Pw, subs, nsub, c.q_plan, c.num_cus, hw, &segw);
-            }
-            // the packed stage's index offsets take ob bits, word 0 above the window's first word
-            // log2(ww) + 37 - Lm bits: 48 in all
-            uint64_t pbmax = 1;
-            for (uint32_t i = 0; i < nsub; ++i) pbmax = std::max<uint64_t>(pbmax, hw[i].nblk ? hw[i].per_blk : 1);
-            uint32_t ob = 0, lw = 0;
-            while ((1ull << ob) < pbmax) ++ob;
-            while ((1u << lw) < ww) ++lw;
-            bool ok = Pw.sparse && need(hw) <= ww && nbw <= kMaxF2Blocks;
-            bool segw_used = false;
-            for (uint32_t i = 0; i < nsub; ++i) segw_used = segw_used || (hw[i].nblk && hw[i].per_blk > segw);
-            if (Pw.wpack) ok = ok && !segw_used && lw + 37 - Pw.Lm + ob <= 48;
-            else ok = ok && segw_used;   // (8-B window stage: the segmented instantiation only)
-            if (ok) {
-                P = Pw;
-                nblk2 = nbw;
-                seg = segw;
-                pk_ob = ob;
-                std::copy(hw, hw + nsub, hd);
-            }
-        }
-    }
-    const bool win = P.wwords != 0;
-    if (nblk2 > kMaxF2Blocks) return hipErrorInvalidValue;
-    const BatchRoute R = route_batch(P, P0, hd, nsub, seg, direct, q, c.q_plan);
-    const bool narrow = R.narrow;
-    if (NP > 8192 || nblk2 > 8192) dbg &= ~256u;   // phase stamps hold 8192 workgroups per kernel
     if (nsub > 1) {
         uint64_t sig = 1469598103934665603ull;
         auto mix = [&](const void* p, size_t b) {
@@ -2775,29 +2085,27 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
     }
     if (nblk2) {
         F2Args a2{d_desc, d_blk, hd[0], nsub, NP, P.Lm, P.b1, bitmap, P.nwords, pcount, pbuf, P.scap, ctr,
-                  R.f2_stage, dbg, P.sparse, seg, (dbg & 256) ? stamps + 8192 * 16 : stamps};
+                  R.f2_stage, dbg, P.sparse, D.seg, (dbg & 256) ? stamps + 8192 * 16 : stamps};
         a2.nsets = P.nsets;
-        a2.wwords = P.wwords;
-        a2.pk_ob = pk_ob;
+        a2.wwords = D.wwords;
         const dim3 g2(nblk2), b2(kF2Threads);
-        const size_t l2 = f2_lds(P, narrow);
-#define F2_GO(MM)                                                    \
-    do {                                                             \
-        if (nsub > 1 && nt) go(1, k_f2_filter<MM, kF2SubsNT>, g2, b2, l2, a2); \
-        else if (nsub > 1) go(1, k_f2_filter<MM, kF2Subs>, g2, b2, l2, a2);   \
-        else go(1, k_f2_filter<MM, kF2One>, g2, b2, l2, a2);                  \
+        const size_t l2 = D.f2_lds;
+#define F2_GO(MM)                                                                           \
+    do {                                                                                    \
+        if (D.f2_src == F2Src::SubsNT) go(1, k_f2_filter<MM, kF2SubsNT>, g2, b2, l2, a2);   \
+        else if (D.f2_src == F2Src::Subs) go(1, k_f2_filter<MM, kF2Subs>, g2, b2, l2, a2);  \
+        else go(1, k_f2_filter<MM, kF2One>, g2, b2, l2, a2);                                \
     } while (0)
-        // window mode: no stage (direct), the packed stage with one final flush (P.wpack), or 8-B segments
-        if (direct && nt) go(1, k_f2_direct<kF2SubsNT>, g2, b2, (size_t)(8 + P.wwords + kDirParts) * 4, a2);
-        else if (direct) go(1, k_f2_direct<kF2Subs>, g2, b2, (size_t)(8 + P.wwords + kDirParts) * 4, a2);
-        else if (win && nt && !P.wpack) go(1, k_f2_filter<kF2Seg, kF2SubsNT, true>, g2, b2, l2, a2);
-        else if (win && nt) go(1, k_f2_filter<kF2Sparse, kF2SubsNT, true>, g2, b2, l2, a2);
-        else if (win && !P.wpack) go(1, k_f2_filter<kF2Seg, kF2Subs, true>, g2, b2, l2, a2);
-        else if (win) go(1, k_f2_filter<kF2Sparse, kF2Subs, true>, g2, b2, l2, a2);
-        else if (R.f2_mode == kF2Narrow) F2_GO(kF2Narrow);
-        else if (R.f2_mode == kF2Seg) F2_GO(kF2Seg);
-        else if (R.f2_mode == kF2Sparse) F2_GO(kF2Sparse);
-        else F2_GO(kF2Dense);
+        switch (D.f2_form) {
+        case F2Form::Direct:   // sorted sub-partitions: no stage
+            if (D.f2_src == F2Src::SubsNT) go(1, k_f2_direct<kF2SubsNT>, g2, b2, l2, a2);
+            else go(1, k_f2_direct<kF2Subs>, g2, b2, l2, a2);
+            break;
+        case F2Form::Narrow: F2_GO(kF2Narrow); break;
+        case F2Form::Seg: F2_GO(kF2Seg); break;
+        case F2Form::Sparse: F2_GO(kF2Sparse); break;
+        case F2Form::Dense: F2_GO(kF2Dense); break;
+        }
 #undef F2_GO
     } else if (ev) {
         (void)hipEventRecord(ev[2], s);
@@ -2806,60 +2114,39 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
     // the base arguments are the whole set's: F4's scan (fallback targets) runs over all its ids
     F3Args a{pbuf, pcount, P.scap, tbuf, tcount, P.tcap, tspill, P.Lm, P.b1, P.Lq, bitmap, P.nwords, c.planes, c.stride,
              c.n, c.tp, c.ts, k, c.gidx, c.base, c.out_idx, c.out_cnt, ctr, fb_list, fb_sub, pstat, tie_hdr, tie_cand, tie_cnt,
-             d_desc, np, dbg, stamps, R.f3_cap, RecOut{}, P.Lm - P.sib, P.nsets};
+             d_desc, np, dbg, stamps, D.f3_cap, RecOut{}, P.Lm - P.sib, P.nsets};
     if (c.out_rec)
         a.rec = RecOut{c.out_rec, c.planes, c.stride, c.rec_gidx, c.rec_base, (nsub == 1 && !c.w0s && !c.skip) ? 1u : 0u,
                        c.skip && c.skip < 32 ? c.skip : 0u, c.nsub ? c.pval << c.sub_bits : c.pval};
-
-    // F3 stages the plan's 6-sigma bound beside F2's narrow stage (which it makes room for), and on
-    // sub-partitioned calls whose partitions run in several rounds of workgroups when that lets 5 or
-    // 6 of them share a CU instead of 4 (F3<8> holds 78 VGPRs: 6 waves per SIMD); F3 is a chain of
-    // round trips per workgroup, so a round of more workgroups shortens the launch (a partition past
-    // the bound sends its targets to the exact fallback, as one past kF3Cap does)
-    if (!narrow && nsub > 1 && k <= 8 && P.fits && P.cap6 < a.cap && NP >= 8u * (uint32_t)std::max(c.num_cus, 1)) {
-        auto per_cu = [](size_t l) { return std::min<size_t>(6, kLdsMax / ((l + 1023) & ~(size_t)1023)); };
-        if (per_cu(f3_lds(P, P.cap6)) > per_cu(f3_lds(P, a.cap))) a.cap = P.cap6;
-    }
-    size_t l3 = f3_lds(P, a.cap);
+    const size_t l3 = D.f3_lds;
     const dim3 g3(NP), b3(kF3Threads);
-    const bool ex = c.n >= k && (k == 8 || k == 16 || k == 32);
 #define F3_GO(KK, DD, SS)                                                     \
     do {                                                                      \
-        if (ex) go(2, k_f3_answer<KK, DD, true, SS>, g3, b3, l3, a);        \
-        else go(2, k_f3_answer<KK, DD, false, SS>, g3, b3, l3, a);          \
+        if (D.f3_exact) go(2, k_f3_answer<KK, DD, true, SS>, g3, b3, l3, a); \
+        else go(2, k_f3_answer<KK, DD, false, SS>, g3, b3, l3, a);           \
     } while (0)
-    if (nsub > 1) {   // (no phase-stamp build for sub-partitioned calls)
-        if (k <= 8) F3_GO(8, false, true);
-        else if (k <= 16) F3_GO(16, false, true);
-        else F3_GO(32, false, true);
-    } else if (dbg) {
-        if (k <= 8) F3_GO(8, true, false);
-        else if (k <= 16) F3_GO(16, true, false);
-        else F3_GO(32, true, false);
-    } else {
-        if (k <= 8) F3_GO(8, false, false);
-        else if (k <= 16) F3_GO(16, false, false);
-        else F3_GO(32, false, false);
-    }
+#define F3_K(DD, SS)                                \
+    do {                                            \
+        switch (D.f3_k) {                           \
+        case 8: F3_GO(8, DD, SS); break;            \
+        case 16: F3_GO(16, DD, SS); break;          \
+        default: F3_GO(32, DD, SS); break;          \
+        }                                           \
+    } while (0)
+    if (D.f3_subs) F3_K(false, true);   // (no phase-stamp build for sub-partitioned calls)
+    else if (D.f3_diag) F3_K(true, false);
+    else F3_K(false, false);
+#undef F3_K
 #undef F3_GO
-    if (dbg & 256) print_phase_profile(P, nblk2, NP, stamps, s);
-    // F4's grid: its workgroups (50 KB of LDS each) hold CUs the other batches' F2 / F3 want,
-    // and on one set (ties answered inline by F3) an empty fallback list leaves them nothing to
-    // do -- 32 workgroups when the context's last completed call listed no target (a hint F4
-    // leaves in mapped host memory; read without a sync, so possibly a call or two old; a list
-    // that appears then is scanned by those 32, still exactly), the full grid otherwise (the
-    // fallback scan's parallelism).  Round 5: 128 -> 32 with the tie-count reads gone, cfg-2 step
-    // 33.6 -> 31.7-31.9 us (profiles/r05/experiments/f4_idle_ab.txt, f4_idle_grid_ab.txt; 16 and
-    // 8 equal).  (a sub-partitioned call fills the chip alone and defers ~1 tie per partition over
-    // 2,048+ partitions: the full grid keeps them at about one per wave)
-    constexpr uint32_t kF4IdleGrid = 32;
-    const uint32_t nfb = (c.fb_hint && *c.fb_hint == 0u && nsub == 1) ? kF4IdleGrid : kFbBlocks;
+    if (dbg & 256) print_phase_profile(nblk2, NP, stamps, s);
     // one set: F3 answers its ties inline, so F4 reads no deferred-tie counts (np_ties 0)
-    const FbArgs fa{fb_rec, fb_done, nfb, nsub > 1 ? NP : 0u, c.fb_hint_dev};
-    const dim3 g4(nfb), b4(kF4Threads);
-    if (k <= 8) go(3, k_f4<8>, g4, b4, 0, a, fa);
-    else if (k <= 16) go(3, k_f4<16>, g4, b4, 0, a, fa);
-    else go(3, k_f4<32>, g4, b4, 0, a, fa);
+    const FbArgs fa{fb_rec, fb_done, D.f4_grid, nsub > 1 ? NP : 0u, c.fb_hint_dev};
+    const dim3 g4(D.f4_grid), b4(kF4Threads);
+    switch (D.f3_k) {
+    case 8: go(3, k_f4<8>, g4, b4, 0, a, fa); break;
+    case 16: go(3, k_f4<16>, g4, b4, 0, a, fa); break;
+    default: go(3, k_f4<32>, g4, b4, 0, a, fa); break;
+    }
     if (c.handles && nsub > 1 && !c.out_rec)   // the whole-set fallback rows -> handles
         k_fb_handles<<<dim3(64), dim3(256), 0, s>>>(c.out_idx, k, fb_list, ctr, c.hinv);
     return hipGetLastError();
@@ -2883,10 +2170,7 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s) {
 // S2's workgroups read this call's while S2 zeroes the other's for the next call.  Prefix
 // shards stream their shifted word-0 plane, as K6 does.
 namespace {
-constexpr uint32_t kSmallQ = 64;
-constexpr uint32_t kSmallCap = 512;                   // candidates per prefix bucket
 constexpr uint32_t kS1Queue = 512;                    // matched ids queued in LDS per block
-constexpr uint32_t kSmallFbBlocks = 32;               // K1 fallback scan workgroups (S2's scan roles)
 constexpr int kS2Threads = scan::WAVES * 64;
 static_assert(kSmallCap <= (uint32_t)kS2Threads, "one bucket slot per S2 thread");
 
@@ -3207,51 +2491,6 @@ __global__ __launch_bounds__(kS2Threads) void k_s2_answer(F3Args a, SmallArgs sa
 }
 
 }  // namespace
-
-// F4 scratch for a list scan: done counters | split records
-static size_t list_scan_bytes(uint32_t k) { return al256((size_t)kFbBlocks * 4) + al256((size_t)kFbBlocks * kFbGroup * k * 24); }
-
-// KS's level: the deepest with >= 4k ids per subtree on uniform ids (K6's rule), at most 31
-uint32_t small_level(uint64_t n, uint32_t k) {
-    uint32_t Ls = 0;
-    while (Ls < 31 && (n >> (Ls + 1)) >= 4ull * k) ++Ls;
-    return Ls;
-}
-
-// The one-set K6 plan of (n, q, k) as a launch on num_cus CUs would use it: words 1..13 of
-// dhtgpu_batch_plan (include/dhtgpu.h).  Host only.
-void batch_plan_words(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t* out) {
-    const BatchPlan P = plan_batch(n, q, k, num_cus, 0);
-    const SubSpec one{nullptr, nullptr, pad_ids(n), n, nullptr, 0u};
-    SubDesc hd[1];
-    uint32_t seg = 0;
-    const uint32_t nblk2 = deal_f2_blocks(P, &one, 1, q, num_cus, hd, &seg);
-    const BatchRoute R = route_batch(P, P, hd, 1, seg, false, q, q);
-    out[1] = P.Lm;
-    out[2] = P.Lm - P.sib;
-    out[3] = P.b1;
-    out[4] = P.Lq;
-    out[5] = P.tcap;
-    out[6] = P.scap;
-    out[7] = P.nsets;
-    out[8] = R.f3_cap;
-    out[9] = R.f2_mode;
-    out[10] = R.f2_stage;
-    out[11] = (uint32_t)hd[0].per_blk;
-    out[12] = nblk2;
-    out[13] = R.f1_two_pass ? 1u : 0u;
-}
-
-bool small_supported(uint64_t n, uint32_t q, uint32_t k) {
-    return q >= 1 && q <= kSmallQ && k >= 1 && k <= DHTGPU_MAX_K_DEV && n >= 1 && n < (1ull << 31);
-}
-
-// cnt[2][kSmallQ] | tab | fb[kSmallFbBlocks][kSmallQ] | F4 scratch (list_scan_bytes(32): done
-// counters first) | cand
-size_t small_bytes() {
-    return al256((size_t)2 * kSmallQ * 4) + al256((size_t)(kSmallQ + 1) * 4) + al256((size_t)kSmallFbBlocks * kSmallQ * 4) +
-           list_scan_bytes(DHTGPU_MAX_K_DEV) + (size_t)kSmallQ * kSmallCap * 16;
-}
 
 hipError_t launch_small_topk(const BatchCall& c, void* sws, uint32_t parity, hipStream_t s) {
     uint8_t* w = static_cast<uint8_t*>(sws);

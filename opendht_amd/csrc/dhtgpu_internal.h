@@ -1,10 +1,14 @@
 // dhtgpu_internal.h -- host-side launch entry points shared between the kernel
-// translation units and the C ABI (api.hip).  Not part of the public ABI.
+// translation units and the C ABI (api.hip).  Not part of the public ABI.  K6's host-only half --
+// the plane geometry, the plan flags, SubSpec, the size queries batch_supported / batch_bytes /
+// batch_clean_bytes / batch_ctr_offset / small_* and batch_plan_words -- is batch_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <mutex>
+
+#include "batch_plan.h"
 
 namespace dhtgpu {
 
@@ -20,15 +24,6 @@ inline hipError_t per_device_once(std::once_flag* flags, void (*set)()) {
     else set();
     return hipSuccess;
 }
-
-// ID-plane geometry: planes are padded to a multiple of kTile ids so that the scan
-// kernel can stream whole tiles without bounds checks.
-constexpr uint32_t kTile = 4096;
-constexpr uint32_t kScanWaves = 8;       // waves per scan workgroup
-constexpr uint32_t kScanTargets = 16;    // targets held (wave-uniform) per wave
-constexpr uint32_t kLdsBytes = 160 * 1024;   // LDS per CU (gfx950)
-
-inline uint64_t pad_ids(uint64_t n) { return ((n + kTile - 1) / kTile) * kTile; }
 
 // keys.hip
 hipError_t launch_gen(uint64_t seed, uint64_t start, uint64_t n, uint32_t* planes,
@@ -138,25 +133,11 @@ hipError_t launch_index_query(const void* ws, uint64_t n, uint32_t B, const uint
                               const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k, uint32_t* out_idx,
                               uint32_t* out_cnt, hipStream_t s);
 
-// batch.hip: K6 per-batch target-prefix filter + exact top-k (no persistent index).
-// n: ids of the largest sub-partition (or of the set); q_plan: the targets one sub-partition
-// is planned for (q / nsub); nsub: sub-partitions served by the call (1: the set itself).
-bool batch_supported(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub = 1, uint32_t pf = 0);
-size_t batch_bytes(uint64_t n, uint32_t q, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub = 1, uint32_t pf = 0);
-// leading workspace bytes that must be zero before a call (the call leaves them zero)
-size_t batch_clean_bytes(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub = 1, uint32_t pf = 0);
-// offset of the shared counters in the workspace head: their words 0..3 (the call's statistics, read by
-// batch_read_stats) stay set after a call, so a head laid out with them elsewhere is zeroed again
-size_t batch_ctr_offset(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub = 1, uint32_t pf = 0);
+// batch.hip: K6 per-batch target-prefix filter + exact top-k (sizes and plan queries: batch_plan.h)
 // stats4 = {fallback targets, survivors, wave-path targets, 0} of the last call on workspace ws
 // (synchronises s)
 hipError_t batch_read_stats(const void* ws, uint64_t n, uint32_t q, uint32_t q_plan, uint32_t k, int num_cus,
                             uint32_t* stats4, hipStream_t s, uint32_t nsub = 1, uint32_t pf = 0);
-// pf (plan flags): kPlanCells -- the sub-partitions' level-cell_level() id counts (launch_cell_counts)
-// are available, which lets the plan mark one level finer with sibling marking (BatchCall::cells);
-// kPlanSorted -- the sub-partitions are sorted by prefix (one bucket set per partition, survivors
-// of an F2 range clustered in whole cells; BatchCall::sorted)
-constexpr uint32_t kPlanCells = 1u, kPlanSorted = 2u;
 uint32_t cell_level();
 // u8 counts (saturated) of the n ids of a shifted word-0 plane per top-cell_level()-bit prefix;
 // scratch: 4 << cell_level() bytes
@@ -166,12 +147,6 @@ hipError_t launch_cell_counts(const uint32_t* w0s, uint64_t n, uint32_t* scratch
 hipError_t launch_cell_spans(const uint32_t* w0s, uint64_t n, uint32_t* spans, hipStream_t s);
 // prefix shards: out[i] = planes word 0 << shift | word 1 >> (32 - shift), i < stride
 hipError_t launch_shift_w0(const uint32_t* planes, uint64_t stride, uint32_t shift, uint32_t* out, hipStream_t s);
-// One prefix sub-partition of a K6 call's id set (host view; see batch.hip SubDesc).
-struct SubSpec {
-    const uint32_t* planes; const uint32_t* w0s;   // unshifted planes; shifted word-0 plane (nullable)
-    uint64_t stride, n;
-    const uint32_t* gidx; uint32_t base;           // result index map (nullable) or offset
-};
 
 constexpr uint32_t kHandleMark = 0x80000000u;   // sets hold < 2^31 ids (batch_supported)
 // DHTGPU_DBG bits the library honours (dhtgpu_ctx::dbg): 256 = phase stamps, 2^23 = K6 for
@@ -232,12 +207,6 @@ hipError_t launch_batch_topk(const BatchCall& c, hipStream_t s);
 // distinct target prefix (K6's results).  sws: small_bytes(), zero before its first use (left
 // zero); parity: alternates between consecutive calls on one workspace (two counter sets);
 // ev (nullable) gets S1 as F2's pair and S2 as F3's, F1 / F4 pairs empty.
-bool small_supported(uint64_t n, uint32_t q, uint32_t k);
-uint32_t small_level(uint64_t n, uint32_t k);   // KS's prefix level Ls
-// words 1..13 of dhtgpu_batch_plan (include/dhtgpu.h) for a one-set K6 call that batch_supported
-// accepts: the plan and what launch_batch_topk makes of it, from the launch's own functions
-void batch_plan_words(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t* out16);
-size_t small_bytes();
 hipError_t launch_small_topk(const BatchCall& c, void* sws, uint32_t parity, hipStream_t s);
 
 // sort.hip: lexicographic sort of an id set (stable LSD radix over the 160-bit keys).

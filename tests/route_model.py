@@ -1,4 +1,5 @@
-"""A numpy model of where one one-set K6 call (opendht_amd/csrc/batch.hip) sends its targets.
+"""A numpy model of where one one-set K6 call (kernels: opendht_amd/csrc/batch.hip; plan and launch
+decision: batch_plan.cpp) sends its targets.
 
 expect(plan, ids, targets, k) applies the documented rules of F1 / F2 / F3 to 32-bit word 0 and
 returns what dhtgpu_batch_topk_timed's stats4 = {fallback targets, survivors, wave-path targets}
@@ -6,7 +7,7 @@ must be, as (lo, hi) bounds: lo == hi unless something order-dependent happens (
 spills, an F2 workgroup loses stage entries, a two-pass F1 bin overflows).  `plan` is the dict of
 opendht_amd.batch_plan(); nothing here looks at the device.  Plain and slow on purpose.
 
-Rules (batch.hip):
+Rules (the kernels of batch.hip):
   F1   a target's partition is its top b1 bits; a partition holds tcap targets, the rest spill
        to the whole-set fallback.  Every target F1 buckets or spills marks its level-Lm cell.
        Two-pass F1 (plan word 13) first groups by coarse bins of ccap targets: a target past a
@@ -47,7 +48,7 @@ def top(w, b):
 
 def f1_coarse(plan, q):
     """(c, ccap) of two-pass F1: coarse bins = top c bits, ccap targets each.  The rule of
-    f1_coarse() in batch.hip: the finest split with >= 512 targets per bin, at most 256 bins,
+    f1_coarse() in batch_plan.cpp: the finest split with >= 512 targets per bin, at most 256 bins,
     c <= b1 and c <= Lm - 5, the fine pass's LDS (2^(Lm-c-5) + 2^(b1-c) words) within 16,384."""
     Lm, b1 = plan["Lm"], plan["b1"]
     lds_ok = lambda c: (1 << (Lm - c - 5)) + (1 << (b1 - c)) <= 16384

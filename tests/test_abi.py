@@ -89,7 +89,7 @@ def test_production_build_has_no_measurement_switches():
     csrc = os.path.join(ROOT, "opendht_amd", "csrc")
     bad = []
     for fn in sorted(os.listdir(csrc)):
-        if not fn.endswith((".hip", ".h")):
+        if not fn.endswith((".hip", ".h", ".cpp")):
             continue
         for no, line in enumerate(open(os.path.join(csrc, fn)), 1):
             if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b.*\bDHT_[A-Z0-9_]+", line):

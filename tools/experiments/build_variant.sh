@@ -1,5 +1,5 @@
 # Build a measurement variant of the in-tree library into opendht_amd/ab/<name>.so: copies csrc to a
-# temp dir, applies a python edit script (which edits batch.hip in its cwd), builds there.  The
+# temp dir, applies a python edit script (which edits the sources in its cwd: batch.hip, batch_plan.h, ...), builds there.  The
 # production sources are never changed (the Makefile takes no extra defines: measurement switches
 # are source edits, kept out of the shipped library).   usage: bash tools/experiments/build_variant.sh edit.py name
 set -e

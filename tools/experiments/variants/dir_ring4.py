@@ -6,5 +6,7 @@ body = s[i:j]
 assert body.count("kF2Ring") == 5
 body = body.replace("kF2Ring", "kDirRingV")
 s = s[:i] + body + s[j:]
-s = s.replace("constexpr uint32_t kDirParts = 4096;", "constexpr uint32_t kDirParts = 4096;\nconstexpr uint32_t kDirRingV = 4;")
+a = "template <uint32_t Src>\n__global__ __launch_bounds__(kF2Threads) void k_f2_direct(F2Args a)"
+assert s.count(a) == 1
+s = s.replace(a, "constexpr uint32_t kDirRingV = 4;\n" + a)
 open("batch.hip", "w").write(s)
