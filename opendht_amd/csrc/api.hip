@@ -156,13 +156,6 @@ std::vector<uint32_t> firsts_planes(const uint8_t* firsts20, uint32_t nb) {
     return fp;
 }
 
-// Sub-partition split of n ids: the smallest s in [1, 8] with 2^s parts of <= 2^24 expected ids.
-uint32_t split_bits(uint64_t n) {
-    uint32_t sb = 1;
-    while (sb < 8 && (n >> sb) > (1ull << 24)) ++sb;
-    return sb;
-}
-
 }  // namespace
 
 struct dhtgpu_ctx {
@@ -668,8 +661,6 @@ int dhtgpu_set_sub_handles(dhtgpu_ctx* c, int on) {
     c->sub_handles = on != 0;
     return DHTGPU_OK;
 }
-
-static bool needs_subs(int num_cus, uint64_t n, uint32_t q, uint32_t k);
 
 // measurement only (not in include/): the phase-stamp buffer of DHTGPU_DBG=256 runs
 int dhtgpu_debug_stamps(dhtgpu_ctx* c, void** dev_ptr, uint64_t* bytes) {
@@ -1240,18 +1231,8 @@ static int batch_run_subs(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const u
     // ids survive): 1.16 -> 0.43 ms per call; the prefix rank (~3 %): 0.149 -> 0.135 ms, the
     // 2^27-id shard 0.157 -> 0.148-0.152 (profiles/r06/experiments).  Below ~2 % survivors a
     // wave's runs would be one or two entries: index order.  Decided once, by the call that
-    // builds them.
-    bool sort = false;
-    {
-        const uint32_t sbe = split_bits(A.n);   // (the split build_subs makes)
-        const uint64_t nsub_e = A.n >> sbe;
-        const double qsub = (double)q / (double)(1u << sbe);
-        uint32_t lm = 0;
-        while (lm < 19 && (nsub_e >> (lm + 1)) >= 4ull * k) ++lm;
-        lm = lm + 1 < 19 ? lm + 1 : 19;
-        sort = 1.0 - std::exp(-qsub / (double)(1ull << lm)) > 0.02;
-    }
-    int r = build_subs(c, A, sort);
+    // builds them (batch_plan.cpp: subs_sort_rule).
+    int r = build_subs(c, A, subs_sort_rule(A.n, q, k));
     if (r) return r;
     const uint32_t sb = c->sub_bits, S = 1u << sb;
     const uint32_t pf = kPlanCells | (c->subs_sorted ? kPlanSorted : 0u);
@@ -1336,10 +1317,6 @@ static int small_run(dhtgpu_ctx* c, const dhtgpu_ctx::ActiveSet& A, const uint32
     if (out_rec)   // (KS stores index rows only: the records are made from them)
         DHT_TRY(launch_rec3(li, (uint64_t)q * k, A.planes, A.stride, idx_base, A.map, out_rec, s));
     return DHTGPU_OK;
-}
-
-static bool needs_subs(int num_cus, uint64_t n, uint32_t q, uint32_t k) {
-    return n > (1ull << 24) && !batch_supported(n, q, k, num_cus) && q <= (1u << 22);
 }
 
 static int batch_run(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t k, uint32_t* out_idx,

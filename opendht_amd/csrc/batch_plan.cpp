@@ -424,6 +424,26 @@ bool batch_supported(uint64_t n, uint32_t q, uint32_t k, int num_cus, uint32_t n
     return f3_lds(P, P.f3cap_wide) <= kLdsBytes && f2_lds(P) <= kLdsBytes;
 }
 
+uint32_t split_bits(uint64_t n) {
+    uint32_t sb = 1;
+    while (sb < 8 && (n >> sb) > (1ull << 24)) ++sb;
+    return sb;
+}
+
+bool needs_subs(int num_cus, uint64_t n, uint32_t q, uint32_t k) {
+    return n > (1ull << 24) && !batch_supported(n, q, k, num_cus) && q <= (1u << 22);
+}
+
+bool subs_sort_rule(uint64_t n, uint32_t q, uint32_t k) {
+    const uint32_t sbe = split_bits(n);   // (the split build_subs makes)
+    const uint64_t nsub_e = n >> sbe;
+    const double qsub = (double)q / (double)(1u << sbe);
+    uint32_t lm = 0;
+    while (lm < 19 && (nsub_e >> (lm + 1)) >= 4ull * k) ++lm;
+    lm = lm + 1 < 19 ? lm + 1 : 19;
+    return 1.0 - std::exp(-qsub / (double)(1ull << lm)) > 0.02;
+}
+
 size_t batch_ctr_offset(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub, uint32_t pf) {
     return ws_layout(plan_batch(n, q_plan, k, num_cus, pf), nsub, 0, k).ctr;
 }

@@ -201,6 +201,14 @@ size_t batch_clean_bytes(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, u
 // offset of the shared counters in the workspace head: their words 0..3 (the call's statistics, read by
 // batch_read_stats) stay set after a call, so a head laid out with them elsewhere is zeroed again
 size_t batch_ctr_offset(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub = 1, uint32_t pf = 0);
+// The routing rules of a call over a set past one plan (api.hip: batch_run, batch_run_subs).
+// Sub-partition split of n ids: the smallest s in [1, 8] with 2^s parts of <= 2^24 expected ids.
+uint32_t split_bits(uint64_t n);
+// the set is served over prefix sub-partitions: no one-set plan accepts the call
+bool needs_subs(int num_cus, uint64_t n, uint32_t q, uint32_t k);
+// the call that builds the sub-partitions sorts them by prefix: more than 2 % of the ids are
+// expected to survive its F2
+bool subs_sort_rule(uint64_t n, uint32_t q, uint32_t k);
 // KS: batches of at most kSmallQ targets (batch.hip: launch_small_topk)
 bool small_supported(uint64_t n, uint32_t q, uint32_t k);
 uint32_t small_level(uint64_t n, uint32_t k);   // KS's prefix level Ls

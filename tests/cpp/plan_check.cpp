@@ -7,9 +7,12 @@
 // (`plan_check -v` prints every line, to find the shape behind a changed hash).
 //
 // Shapes: the one-set grid; sub-partitioned shapes with span tables (uneven and empty
-// sub-partitions, every plan-flag combination); the shapes of bench.py's cfg-3 legs and of the
-// sub-partitioned tests in tests/test_gpu_scale.py; span tables that refuse k_f2_direct on each of
-// its three conditions.
+// sub-partitions, every plan-flag combination); the shapes of bench.py's cfg-3 legs and further
+// recorded sets of 2^25 .. 1.25e8 ids, split and planned whatever route the library gives them; span
+// tables that refuse k_f2_direct on each of its three conditions; the sub-partitioned shapes the
+// GPU tests run (`plan_check [-v] tests/golden/sub_shapes.txt`), each with the route the library
+// takes (batch_run's order of decisions), its split and the order its sub-partitions are built
+// in; and the constructed sub-partition sizes and span tables of tests/test_gpu_subs.py.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +20,8 @@
 #include <stdarg.h>
 
 #include <algorithm>
+#include <fstream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -161,6 +166,17 @@ static void run(const Case& c, bool named = false) {
         const uint32_t w = D.wwords;
         CHECK(w >= 64 && w <= 2048 && (w & (w - 1)) == 0 && 2 * w <= P.nwords, "%s: window %u of %u words", c.tag, w, P.nwords);
         CHECK(P.nsets == 1, "%s: direct with %u bucket sets", c.tag, P.nsets);
+        // k_f2_direct counts a range's partitions p_first + pl, pl < kDirParts, in LDS: the window
+        // direct_window accepted (<= 2,045 words + 3) bounds the level-Lm cells between a range's
+        // first and last id, hence the partitions between them, by (cells >> (Lm - b1)) + 1
+        for (uint32_t i = 0; i < nsub; ++i) {
+            if (!hd[i].nblk) continue;
+            uint32_t j = 0;
+            while (j < 31 && (1ull << j) < hd[i].per_blk) ++j;
+            const uint32_t cells = (c.spans[i * 32 + j] >> (kMaxLm - P.Lm)) + 1;
+            CHECK((cells >> (P.Lm - P.b1)) + 1 < kDirParts, "%s: sub %u: a range over %u level-%u cells, partitions of %u",
+                  c.tag, i, cells, P.Lm, 1u << (P.Lm - P.b1));
+        }
     } else {
         CHECK(D.R.f2_stage >= 1 && f2_fixed_words(P.nwords, 1u << P.b1) * 4 + (size_t)D.R.f2_stage * (D.R.narrow ? 6 : 8) == D.f2_lds,
               "%s: F2 LDS", c.tag);
@@ -196,8 +212,50 @@ static Case subs_case(const char* tag, uint64_t n, uint32_t sb, uint32_t q, uint
     return c;
 }
 
+// What dhtgpu_batch_plan reports in word 0 (api.hip, batch_run's order of decisions)
+static uint32_t route_of(uint64_t n, uint32_t q, uint32_t k, int cus) {
+    if (small_supported(n, q, k)) return 0;
+    if (needs_subs(cus, n, q, k)) return 2;
+    return batch_supported(n, q, k, cus) ? 1 : 3;
+}
+
+// tests/golden/sub_shapes.txt: `name n q k [q_build]` per line.  For each shape at 256 CUs: the
+// route, the split and whether the sub-partitions are built sorted (by the call itself, or by the
+// earlier call of q_build targets), then the decision over even sub-partitions with that order
+// (sorted: uniform span tables, as subs_case makes them)
+static void listed_shapes(const char* path) {
+    std::ifstream in(path);
+    if (!in) {
+        fprintf(stderr, "plan_check: cannot read %s\n", path);
+        ++g_bad;
+        return;
+    }
+    std::string line;
+    std::vector<std::string> names;   // (the tags outlive the loop)
+    while (std::getline(in, line)) {
+        if (line.empty() || line[0] == '#') continue;
+        std::istringstream is(line);
+        std::string name;
+        unsigned long long n = 0;
+        uint32_t q = 0, k = 0, qb = 0;
+        is >> name >> n >> q >> k;
+        if (!(is >> qb)) qb = q;
+        CHECK(n && q && k, "%s: malformed line", line.c_str());
+        if (!n || !q || !k) continue;
+        names.push_back(name);
+        const uint32_t sb = split_bits(n);
+        const bool sorted = subs_sort_rule(n, qb, k);
+        printf("sub-shape %s n %llu q %u k %u q_build %u | route %u nsub %u sorted %d\n", name.c_str(), n, q, k, qb,
+               route_of(n, q, k, 256), 1u << sb, sorted ? 1 : 0);
+        run(subs_case(names.back().c_str(), n, sb, q, k, 256, kPlanCells | (sorted ? kPlanSorted : 0u), 1.25, 0), true);
+    }
+}
+
 int main(int argc, char** argv) {
-    g_verbose = argc > 1 && std::string(argv[1]) == "-v";
+    int arg = 1;
+    g_verbose = argc > arg && std::string(argv[arg]) == "-v";
+    if (g_verbose) ++arg;
+    const char* shapes = argc > arg ? argv[arg] : nullptr;
     // 1. the one-set grid
     const uint64_t ns[] = {1, 5, 40, 1000, 1ull << 15, (1ull << 17) - 1, 1ull << 17, 1ull << 20, (1ull << 24) - 3,
                            1ull << 24, 22400000ull, 1ull << 25, 1ull << 27, (1ull << 31) - 1};
@@ -218,7 +276,9 @@ int main(int argc, char** argv) {
             run(Case{"one-flags", {1ull << 24}, 65536, 65536, 8, 256, 0u, {}, dbg, idle}, true);
             run(Case{"one-flags", {1ull << 20}, 1u << 20, 1u << 20, 16, 256, 0u, {}, dbg, idle}, true);
         }
-    // 2. bench.py's cfg-3 legs and the sub-partitioned tests of tests/test_gpu_scale.py (uniform ids)
+    // 2. bench.py's cfg-3 legs and further recorded sets (uniform ids), split as the library would
+    // split them and planned as sub-partitions whichever route it gives the shape (the shapes the
+    // tests run, with their routes: 5. below)
     struct { const char* tag; uint64_t n; uint32_t q, k; } known[] = {
         {"cfg3-shard", 1ull << 27, 131072, 8},        {"cfg3-prefix-rank", 125000000ull, 131072, 8},
         {"cfg3-broadcast-rank", 125000000ull, 1u << 20, 8}, {"scale-2p26", 1ull << 26, 1u << 18, 8},
@@ -268,6 +328,36 @@ int main(int argc, char** argv) {
         run(subs_case("direct-refused-half", 1ull << 17, 2, 1u << 14, 8, 256, kPlanSorted, 1.0, 0), true);
         run(subs_case("direct-refused-blocks", ((1ull << 24) - 1) << 7, 7, 1u << 19, 8, 200000, kPlanCells | kPlanSorted, 1.0, 0), true);
         run(subs_case("direct-taken", 1ull << 27, 3, 1u << 20, 8, 256, kPlanCells | kPlanSorted, 1.0, 0), true);
+    }
+    // 5. the sub-partitioned shapes of the GPU tests
+    if (shapes) listed_shapes(shapes);
+    // 6. constructed sub-partitions of tests/test_gpu_subs.py and tests/test_gpu_scale.py (2^26 ids,
+    // 4 sub-partitions, built sorted)
+    {
+        const uint32_t pf = kPlanCells | kPlanSorted;
+        // ids [0, 2^19) of the stream replaced by 2^19 ids of one 26-bit prefix (sub-partition 1):
+        // every sub-partition loses about 2^17 stream ids, the spans are those of the uniform rest (the
+        // cluster lies in one level-19 cell) -- direct is still taken, and the cluster's partition is
+        // shared by the three or more workgroups whose ranges it fills
+        Case wg3 = subs_case("subs-one-partition-three-workgroups", 1ull << 26, 2, 1u << 17, 8, 256, pf, 1.25, 0);
+        for (uint32_t i = 0; i < 4; ++i) {
+            wg3.n[i] = (1ull << 24) - (1ull << 17);
+            uniform_spans(wg3.n[i], 1.25, wg3.spans.data() + (size_t)i * 32);
+        }
+        wg3.n[1] += 1ull << 19;
+        run(wg3, true);
+        // ids [0, 2^16) replaced by copies of other stream ids: equal ids, spans unchanged
+        run(subs_case("subs-equal-ids", 1ull << 26, 2, 1u << 17, 8, 256, pf, 1.25, 0), true);
+        // test_subpartition_with_fewer_than_k_ids: sub-partition 3 emptied down to 5 ids (they span most
+        // of its 2^19 cells), its other ids moved into sub-partition 1 -- the window of the 5-id
+        // sub-partition's one workgroup is past 2,048 words, so direct is refused: the staged F2 over
+        // sorted sub-partitions
+        Case few = subs_case("subs-five-id-sub-partition", 1ull << 26, 2, 1u << 18, 8, 256, pf, 1.25, 0);
+        few.n[1] = (1ull << 25) - 5;
+        few.n[3] = 5;
+        uniform_spans(few.n[1], 1.25, few.spans.data() + 32);
+        for (uint32_t j = 0; j < 32; ++j) few.spans[3 * 32 + j] = j < 3 ? 150000u * j : 350000u;
+        run(few, true);
     }
     printf("F2 forms: direct %u narrow %u segmented %u sparse %u dense %u\n", g_forms[0], g_forms[1], g_forms[2], g_forms[3],
            g_forms[4]);

@@ -6,6 +6,7 @@ import pytest
 
 import merge_util as MU
 import oracle as O
+from sub_shapes import assert_subs, shape
 
 pytestmark = pytest.mark.gpu
 
@@ -393,7 +394,7 @@ def test_prefix_shard_masked():
 # ---- 9. sub-partitioned view ----------------------------------------------------------------
 def test_subpartitioned_view():
     """3 * 2^24 ids, every third rejected: a view of 2^25 ids, 2^18 targets -- the shape of
-    test_subpartitions_k_sequence_fresh_context reached through the view.  At k = 8 one K6 plan
+    test_subpartition_overfull reached through the view.  At k = 8 one K6 plan
     serves 2^25 ids on a 256-CU device; at k = 32 it cannot (batch_supported), so that is the call
     that builds the two sub-partitions from the view: both are checked."""
     import opendht_amd
@@ -412,8 +413,11 @@ def test_subpartitioned_view():
         sub = ids[np.flatnonzero(mask)]
         del ids
         first = {}
+        assert (1 << 25, q, 32) == shape("view-k32.sorted")
         for k in (8, 32):
             assert c.sub_handles_active(q, k) == 0
+            if k == 32:   # (the plan query takes the ids the call sees: the view's)
+                assert_subs(c, 1 << 25, q, k)
             got, cnt = c.batch_topk(tg, k)
             sc, scnt = c.topk(tg, k)
             assert_rows(got, cnt, sc, scnt, f"view vs masked K1, k={k}")
@@ -426,6 +430,8 @@ def test_subpartitioned_view():
         c.update_accept(np.array([off], np.uint32), 0)
         assert c.num_accepted == (1 << 25) - 1
         for k in (32, 8):
+            if k == 32:
+                assert_subs(c, (1 << 25) - 1, q, k)
             got2, cnt2 = c.batch_topk(tg, k)
             sc2, scnt2 = c.topk(tg, k)
             assert_rows(got2, cnt2, sc2, scnt2, f"after update_accept, k={k}")
@@ -490,6 +496,7 @@ def test_context_close_returns_device_memory():
             c.set_accept(mask)
             c.batch_topk(tg, k)      # the view (one K6 plan serves its 22.4 M ids)
             c.set_accept(None)
+            assert_subs(c, n, q, k)
             c.batch_topk(tg, k)      # the set's sub-partitions
             c.index_topk(tg[:64], k)   # the K4 index
             c.cache_set(cache)

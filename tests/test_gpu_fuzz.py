@@ -10,6 +10,7 @@ import pytest
 
 import merge_util as MU
 import oracle as O
+from sub_shapes import assert_subs, shape
 from test_gpu_parity import check_topk
 
 pytestmark = pytest.mark.gpu
@@ -196,13 +197,15 @@ def test_record_shards_merge_random(ctx, seed):
 
 @pytest.mark.parametrize("seed", range(4))
 def test_subpartitioned_random(ctx, seed):
-    """Sets past one K6 plan at random shapes (n in (2^24, 2^26], q in [2^14, 2^17], random k):
-    the library sub-partitions them; whole batch == K1 scan, a sample == the oracle."""
+    """Sets past one K6 plan at random shapes (n in [2^26, 2^26 + 2^24], q in [2^17, 2^18], random
+    k; sub_shapes.txt pins the corners fuzz-lo and fuzz-hi): the library sub-partitions them (4 or 8
+    sub-partitions); whole batch == K1 scan, a sample == the oracle."""
     rng = np.random.default_rng(60_000 + seed)
-    n = int(rng.integers((1 << 24) + 1, (1 << 26) + 1))
-    q = int(rng.integers(1 << 14, (1 << 17) + 1))
+    n = int(rng.integers(shape("fuzz-lo.sorted")[0], shape("fuzz-hi.sorted")[0] + 1))
+    q = int(rng.integers(shape("fuzz-lo.sorted")[1], shape("fuzz-hi.sorted")[1] + 1))
     k = int(rng.integers(1, 33))
     ctx.gen_ids(700 + seed, n)
+    assert_subs(ctx, n, q, k)
     tg = rng.integers(0, 256, size=(q, 20), dtype=np.uint8)
     got, cnt = ctx.batch_topk(tg, k)
     sc, scnt = ctx.topk(tg, k)
@@ -215,15 +218,17 @@ def test_subpartitioned_random(ctx, seed):
 def test_subpartition_overfull():
     """2^25 ids (two prefix sub-partitions by the top bit) with 75 % of them moved into
     sub-partition 0 (~2^24.6 ids: more than one K6 plan serves): the call must still be exact
-    (K6 == K1 scan on the whole batch, a sample == the oracle)."""
+    (K6 == K1 scan on the whole batch, a sample == the oracle).  2^18 targets at k = 32: the fewest
+    with which 2^25 ids are sub-partitioned at all."""
     import opendht_amd
-    n, q, k = 1 << 25, 1 << 17, 8
+    n, q, k = shape("overfull.sorted")
     ids = O.gen_ids(8080, n)
     ids[: 3 * n // 4, 0] &= 0x7F
     tg = O.gen_ids(8081, q)
     c = opendht_amd.Context(0)
     try:
         c.set_ids(ids)
+        assert_subs(c, n, q, k)
         got, cnt = c.batch_topk(tg, k)
         sc, scnt = c.topk(tg, k)
         assert np.array_equal(cnt, scnt) and np.array_equal(got, sc)
@@ -264,14 +269,16 @@ def test_search_batch_random(ctx, seed):
 
 @pytest.mark.parametrize("seed", range(3))
 def test_subpartitioned_random_handles(ctx, seed):
-    """Random sub-partitioned shapes with sub-partition handles on: when the call returns handles,
-    mapping them back (dhtgpu_handles_to_indices_dev) gives exactly the K1 scan's indices."""
+    """Random sub-partitioned shapes (the range of test_subpartitioned_random) with sub-partition
+    handles on: the call returns handles, and mapping them back (dhtgpu_handles_to_indices_dev)
+    gives exactly the K1 scan's indices."""
     import torch
     rng = np.random.default_rng(61_000 + seed)
-    n = int(rng.integers((1 << 25) + 1, (1 << 26) + 1))
-    q = int(rng.integers(1 << 17, (1 << 18) + 1))
+    n = int(rng.integers(shape("fuzz-lo.sorted")[0], shape("fuzz-hi.sorted")[0] + 1))
+    q = int(rng.integers(shape("fuzz-lo.sorted")[1], shape("fuzz-hi.sorted")[1] + 1))
     k = int(rng.integers(1, 33))
     ctx.gen_ids(710 + seed, n)
+    assert_subs(ctx, n, q, k)
     tg = rng.integers(0, 256, size=(q, 20), dtype=np.uint8)
     sc, scnt = ctx.topk(tg, k)
     ctx.set_sub_handles(True)
@@ -281,9 +288,7 @@ def test_subpartitioned_random_handles(ctx, seed):
     finally:
         ctx.set_sub_handles(False)
     assert np.array_equal(cnt, scnt), (seed, n, q, k)
-    if not active:   # one K6 plan served it: ordinary indices
-        assert np.array_equal(h, sc)
-        return
+    assert active, (seed, n, q, k)
     dev = torch.device("cuda", 0)
     hd = torch.from_numpy(h.reshape(-1).view(np.int32)).to(dev)
     out = torch.empty_like(hd)

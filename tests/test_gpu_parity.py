@@ -1110,8 +1110,8 @@ def test_f4_half_grid_then_fallback_list():
 
 def test_dbg_bits_leave_results_unchanged(monkeypatch):
     """DHTGPU_DBG with every bit set (the variable is read at context creation and masked to the
-    diagnostics bits; tests/test_abi.py pins the mask): K6, KS (here: K6 on small batches, bit 2^23)
-    and the sub-partitioned route return exactly the oracle's nodes."""
+    diagnostics bits; tests/test_abi.py pins the mask): K6 at 3,000 targets and, through bit 2^23, on
+    the small batches KS would serve return exactly the oracle's nodes (2^20 ids: one set)."""
     import opendht_amd
     monkeypatch.setenv("DHTGPU_DBG", str(0xFFFFFFFF & ~256))   # 256 (stamps) prints to stderr: left out
     ids = O.gen_ids(4242, 1 << 20)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from sub_shapes import assert_subs, shape
 
 pytestmark = pytest.mark.gpu
 
@@ -33,8 +34,9 @@ def test_cfg3_shard_2p27(ctx):
     sample == std::partial_sort(xorCmp); the record form + K3 merge gives the same answer."""
     import torch
     import opendht_amd
-    n, q, k = 1 << 27, 131072, 8
+    n, q, k = shape("cfg3-shard.sorted")
     ctx.gen_ids(777, n)
+    assert_subs(ctx, n, q, k)
     tg = O.gen_ids(778, q)
     got, cnt = ctx.batch_topk(tg, k)
     assert np.all(cnt == k)
@@ -95,6 +97,7 @@ def test_cfg3_full_1e9_range_shards():
         for r in range(world):
             lo, hi = sharding.shard_range(n, world, r)
             c.gen_ids(seed, hi - lo, start=lo)
+            assert_subs(c, hi - lo, q, k)
             c.batch_topk_dev(tp.data_ptr(), ts, q, k, None, None, rec[r].data_ptr(), lo, c.stream)
             torch.cuda.synchronize()
     t_shards = time.perf_counter() - t0
@@ -112,6 +115,7 @@ def test_cfg3_full_1e9_range_shards():
     t0 = time.perf_counter()
     with opendht_amd.Context(0) as c:
         c.gen_ids(seed, n)
+        assert_subs(c, n, q, k)
         one, ocnt = c.batch_topk(tg, k)
     t_one = time.perf_counter() - t0
     assert np.array_equal(ocnt, gcnt)
@@ -127,13 +131,17 @@ def test_cfg3_full_1e9_range_shards():
 def test_subpartition_with_fewer_than_k_ids(ctx):
     """2^26 ids whose prefix-11 quarter is emptied down to 5 ids, 2^18 targets (K6 plans this
     over 4 sub-partitions): targets with prefix 11 must take ids from outside their
-    sub-partition, so the library routes them to the K1 scan over the whole set."""
-    n, q, k = 1 << 26, 1 << 18, 8
+    sub-partition, so the library routes them to the K1 scan over the whole set.  The
+    sub-partitions are built sorted, and the 5 ids span most of their sub-partition's level-19
+    cells: k_f2_direct's window would pass 2,048 words, so this call runs the staged F2 over sorted
+    sub-partitions (tests/golden/k6_decide.txt: subs-five-id-sub-partition, form 2)."""
+    n, q, k = shape("scale-2p26-k8.sorted")
     ids = O.gen_ids(2626, n)
     top = ids[:, 0] >> 6
     move = np.nonzero(top == 3)[0][5:]
     ids[move, 0] &= 0x7F                     # prefix 11 -> 01: sub-partition 3 keeps 5 ids
     ctx.set_ids(ids)
+    assert_subs(ctx, n, q, k)
     tg = O.gen_ids(2627, q)
     got, cnt = ctx.batch_topk(tg, k)
     sc, scnt = ctx.topk(tg, k)
@@ -148,14 +156,17 @@ def test_subpartitions_k_sequence_fresh_context():
     in the workspace move with k (they sit after the k-sized fallback records), and a call that
     reused the cached table signature without re-uploading read stale descriptors (a fault, once
     the workspace was large enough not to be reallocated).  k = 32 first (the largest workspace),
-    then smaller k on the same context: every call == K1 scan."""
+    then smaller k on the same context: every call == K1 scan.  2^26 ids and 2^17 targets: every k
+    of the sequence is sub-partitioned (4 sub-partitions), so each call follows a sub-partitioned
+    one of another k."""
     import opendht_amd
-    n, q = 1 << 25, 1 << 18   # q large enough that one plan cannot serve: 2 sub-partitions
+    n, q, _ = shape("kseq-k32.sorted")
     c = opendht_amd.Context(0)
     try:
         c.gen_ids(3131, n)
         tg = O.gen_ids(3132, q)
         for k in (32, 1, 3, 8, 16, 3):
+            assert_subs(c, n, q, k)
             got, cnt = c.batch_topk(tg, k)
             sc, scnt = c.topk(tg, k)
             assert np.array_equal(cnt, scnt) and np.array_equal(got, sc), k
@@ -168,8 +179,9 @@ def test_subpartitions_larger_k(ctx, k):
     """2^26 ids, 2^18 targets (4 prefix sub-partitions, one K6 launch sequence) at k = 1, 3, 16
     and 32 (k < 4: many empty mark-level subtrees, so the fallback scan's per-target form runs
     with its split cap): whole batch == K1 scan, a sample == std::partial_sort(xorCmp)."""
-    n, q = 1 << 26, 1 << 18
+    n, q = shape(f"scale-2p26-k{k}.sorted")[:2]
     ctx.gen_ids(2929, n)
+    assert_subs(ctx, n, q, k)
     tg = O.gen_ids(2930, q)
     got, cnt = ctx.batch_topk(tg, k)
     sc, scnt = ctx.topk(tg, k)
@@ -186,7 +198,7 @@ def test_subpartition_deficient_subtree_targets(ctx):
     F3 lists them for the fallback scan, which for so short a list scans each target's own
     sub-partition (it holds >= k ids, so their top-k lies inside it).  Whole batch == K1 scan,
     the two targets == std::partial_sort(xorCmp)."""
-    n, q, k = 1 << 26, 1 << 18, 8
+    n, q, k = shape("scale-2p26-k8.sorted")
     ids = O.gen_ids(2828, n)
     tg = O.gen_ids(2829, q)
     key = lambda a: ((a[:, 0].astype(np.uint32) << 16) | (a[:, 1].astype(np.uint32) << 8) | a[:, 2]) >> 4
@@ -197,6 +209,7 @@ def test_subpartition_deficient_subtree_targets(ctx):
         ids[inside, 2] ^= 0x10           # bit 19: into the sibling subtree, same sub-partition
         ik = key(ids)
     ctx.set_ids(ids)
+    assert_subs(ctx, n, q, k)
     got, cnt = ctx.batch_topk(tg, k)
     sc, scnt = ctx.topk(tg, k)
     assert np.array_equal(cnt, scnt) and np.array_equal(got, sc)
@@ -204,36 +217,45 @@ def test_subpartition_deficient_subtree_targets(ctx):
     assert np.array_equal(got[picks], want) and np.array_equal(cnt[picks], wcnt)
 
 
-@pytest.mark.parametrize("q", [65536, 262144])
-def test_subpartition_sibling_marking(ctx, q):
-    """Sibling marking (round 6): 31.25 M ids = 2 prefix sub-partitions of ~1.56e7 with 65,536
-    targets plan one level finer than the 4k rule (level-19 cells of ~30 ids) because the
+@pytest.mark.parametrize("name", ["sibling-min-q.sorted", "sibling.sorted"])
+def test_subpartition_sibling_marking(ctx, name):
+    """Sibling marking (round 6): 4e7 ids = 4 prefix sub-partitions of ~1e7 with 327,680 targets (the
+    fewest that are sub-partitioned at this size) and with 2^19 plan one level finer than the 4k
+    rule (level-19 cells of ~19 ids; k6_decide.txt: sib = 1 for both) because the
     sub-partitions carry their level-19 cell counts: a target whose own cell holds < k ids marks the
     sibling cell too and answers from the complete pair.  Crafted: 48 targets' cells emptied down
     to 3 ids (moved into the sibling: the pair keeps them all), 16 targets' whole pairs emptied
     down to 2 + 2 ids (the pair is short: F3's fallback scan of the sub-partition).  Whole batch
-    == K1 scan; the crafted targets and a sample == std::partial_sort(xorCmp).  q = 262,144: the
-    survivors are dense (~22 %), so the sub-partitions are built prefix-sorted and F2 runs its
-    bitmap window (the cfg-3 broadcast rank's route)."""
-    n, k = 31_250_000, 8
+    == K1 scan; the crafted targets and a sample == std::partial_sort(xorCmp).  The survivors are
+    dense at both counts (15 % and 22 %), so the sub-partitions are built prefix-sorted and F2 runs
+    its bitmap window (the cfg-3 broadcast rank's route); no smaller set is sub-partitioned with
+    sibling marking below ~6.5e5 targets."""
+    n, q, k = shape(name)
     ids = O.gen_ids(3434, n)
     tg = O.gen_ids(3435, q)
-    key = lambda a: ((a[:, 0].astype(np.uint32) << 12) | (a[:, 1].astype(np.uint32) << 4) | (a[:, 2] >> 4))
+    # a level-19 cell of a sub-partition: the 2 sub-partition bits and the next 19
+    key = lambda a: ((a[:, 0].astype(np.uint32) << 13) | (a[:, 1].astype(np.uint32) << 5) | (a[:, 2] >> 3))
     ik, tk = key(ids), key(tg)
     rng = np.random.default_rng(3436)
     picks = rng.choice(q, 64, replace=False)
     for j, t in enumerate(picks):
         cell = tk[t]
+        moved = []
         if j < 48:   # the cell keeps 3 ids, the rest move to the sibling cell (bit 19)
             inside = np.nonzero(ik == cell)[0][3:]
-            ids[inside, 2] ^= 0x10
+            ids[inside, 2] ^= 0x08
+            moved.append(inside)
         else:        # cell and sibling keep 2 ids each, the rest move to the other pair (bit 18)
             for c_ in (cell, cell ^ 1):
                 inside = np.nonzero(ik == c_)[0][2:]
-                ids[inside, 2] ^= 0x20
-        ik = key(ids)
+                ids[inside, 2] ^= 0x10
+                moved.append(inside)
+        moved = np.concatenate(moved)
+        ik[moved] = key(ids[moved])   # (the keys of the ids that moved: the others' stand)
+    assert np.array_equal(ik, key(ids))
     assert len(np.unique(ids, axis=0)) == n
     ctx.set_ids(ids)
+    assert_subs(ctx, n, q, k)
     got, cnt = ctx.batch_topk(tg, k)
     sc, scnt = ctx.topk(tg, k)
     assert np.array_equal(cnt, scnt)
@@ -244,17 +266,21 @@ def test_subpartition_sibling_marking(ctx, q):
     assert np.array_equal(got[rows], want) and np.array_equal(cnt[rows], wcnt)
 
 
-@pytest.mark.parametrize("n,q", [(1 << 22, 1 << 17), (1 << 25, 1 << 18)])
+@pytest.mark.parametrize("n,q", [(1 << 22, 1 << 17), (1 << 25, 1 << 19)])
 def test_f1_two_pass_clustered_targets(ctx, n, q):
     """F1's two-pass form (batches of >= 2^17 targets, round 6: coarse bins by workgroup-level
     reservations, then one workgroup per bin marking the bitmap and ranking the partitions in LDS):
     a quarter of the targets share their top 12 bits (their coarse bin overflows: those targets
     spill to the fallback scan from the first pass), and groups of 96, 256, 700 and 2,048 targets
     each share a 22-bit prefix (one partition's bucket overflows in the second pass, or the bin in
-    the first, by size); one set and 2 sub-partitions.  Whole batch == K1 scan, a sample of each
+    the first, by size); one set and 2 sub-partitions (2^25 ids need 2^19 targets to be
+    sub-partitioned at k = 8).  Whole batch == K1 scan, a sample of each
     group == std::partial_sort(xorCmp)."""
     k = 8
     ctx.gen_ids(3737, n)
+    if n > 1 << 24:
+        assert (n, q, k) == shape("two-pass-2p25.sorted")
+        assert_subs(ctx, n, q, k)
     tg = O.gen_ids(3738, q)
     a = q // 4
     tg[:a, 0] = 0xA7
@@ -458,6 +484,7 @@ def _handles_vs_indices(c, tg, k, base=0):
     """The same call with and without sub-partition handles; the handles mapped back on the
     device (dhtgpu_handles_to_indices_dev) must equal the indices, row for row."""
     import torch
+    assert_subs(c, c.num_ids, tg.shape[0], k)
     c.set_sub_handles(False)
     want, wcnt = c.batch_topk(tg, k)
     c.set_sub_handles(True)
@@ -487,7 +514,7 @@ def test_sub_handles_map_back(ctx, k):
     over 4 sub-partitions, 2^18 targets; every handle maps back to the index the call returns
     without handles (k < 4: the fallback scan's split merge), handles are a bijection onto [0, n)
     (two different ids never share one)."""
-    n, q = 1 << 26, 1 << 18
+    n, q = shape(f"scale-2p26-k{k}.sorted")[:2]
     ctx.gen_ids(3737, n)
     tg = O.gen_ids(3738, q)
     h = _handles_vs_indices(ctx, tg, k)
@@ -501,7 +528,7 @@ def test_sub_handles_whole_set_fallback(ctx):
     F4 scans the context's planes and converts its rows to handles by a binary search in the
     sub-partitions' index maps); and the prefix-shard form (global stream indices on the way
     back)."""
-    n, q, k = 1 << 26, 1 << 18, 8
+    n, q, k = shape("scale-2p26-k8.sorted")
     ids = O.gen_ids(2626, n)
     top = ids[:, 0] >> 6
     move = np.nonzero(top == 3)[0][5:]
@@ -519,8 +546,9 @@ def test_sub_handles_record_form_unaffected(ctx):
     """Record form ignores handles (records carry global indices for the cross-rank merge)."""
     import torch
     import opendht_amd
-    n, q, k = 1 << 26, 1 << 18, 8
+    n, q, k = shape("scale-2p26-k8.sorted")
     ctx.gen_ids(3737, n)
+    assert_subs(ctx, n, q, k)
     tg = O.gen_ids(3738, q)
     dev = torch.device("cuda", 0)
     ts = (q + 63) // 64 * 64
