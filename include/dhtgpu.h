@@ -26,6 +26,12 @@
  *   dhtgpu_search_insert   Search::insertNode (src/search.h:636-722) itself, batched over searches
  *   dhtgpu_table_stats     InfoHash::lowbit + RoutingTable::depth of every bucket, on the device
  *   dhtgpu_cache_set/_nodes  NodeCache's map (node_cache.h:43) sorted on the device + getCachedNodes
+ *   dhtgpu_rt_set/_set_good  the RoutingTable itself (include/opendht/routing_table.h:45-94) kept on
+ *                          the device between calls, with the Node::isGood(now) snapshot
+ *   dhtgpu_rt_reply        Dht::onFindNode (src/dht.cpp:2128-2138) / onGetValues' (:2141-2161) answer:
+ *                          findClosestNodes(target, now, TARGET_NODES) + bufferNodes, fused
+ *   dhtgpu_rt_closer       the closeness tests of Dht::maintainStorage (src/dht.cpp:1862-1879) and
+ *                          Dht::onAnnounce (:2293-2294): findClosestNodes + xorCmp(nodes.back(), myid)
  *
  * Threading (mirrors the reference, src/dhtrunner.cpp:115-150): one context per
  * thread, or external locking; every host-pointer call is synchronous.
@@ -298,6 +304,64 @@ int dhtgpu_find_closest(dhtgpu_ctx* ctx, uint32_t nb, const uint8_t* firsts20,
                         const uint32_t* bucket_off, const uint8_t* node_ids20,
                         const uint8_t* good, const uint8_t* targets20_be, uint32_t q,
                         uint32_t count, uint32_t* out_idx, uint32_t* out_cnt);
+
+/* ---- K1w: the resident routing table -------------------------------------------------------- */
+/* The table of dhtgpu_find_closest kept on the device between calls, so that a responder's
+ * find_node / get answers and the storage closeness tests cross PCIe with their targets only.
+ * One table per context (one context per address family), private to the rt entry points: the
+ * k-NN id set, the accept mask and the NodeCache mirror are not touched, nor do they touch it.
+ *
+ * dhtgpu_rt_set uploads a snapshot in bucket list order -- nb <= 256 buckets, firsts20[nb*20]
+ * (Bucket::first), bucket_off[nb+1] non-decreasing (bucket b owns nodes [off[b], off[b+1]) of
+ * node_ids20), exactly as dhtgpu_find_closest takes them -- together with myid20 (Dht::myid) and,
+ * nullable, node_tail: node i's address || port bytes at node_tail[i*(alen+2)], laid out like the
+ * node_tail of dhtgpu_buffer_nodes_ids (alen = 4 for af 4, 16 for af 6; af = 0 when node_tail is
+ * NULL, and dhtgpu_rt_reply then returns DHTGPU_EINVAL).  Every node starts good.  nb == 0 is a
+ * valid, empty table.  version != 0 equal to the last upload's, with the same nb and node count,
+ * skips the upload (the rule of dhtgpu_cache_set: the caller bumps it whenever the table changes).
+ * Synchronous; like dhtgpu_set_ids it must not be called while rt calls are in flight. */
+int dhtgpu_rt_set(dhtgpu_ctx* ctx, const uint8_t* myid20, uint32_t nb, const uint8_t* firsts20,
+                  const uint32_t* bucket_off, const uint8_t* node_ids20, const uint8_t* node_tail, uint32_t af,
+                  uint64_t version);
+/* The Node::isGood(now) snapshot (src/node.cpp:42-47), which changes between calls while the
+ * table does not: good[nn] (host; nonzero = good) replaces every bit; dhtgpu_rt_update_good sets
+ * good[idx[j]] = val[j] for m entries (host arrays; idx < nn else DHTGPU_EINVAL, nothing applied;
+ * distinct idx).  Both run on the context's stream without synchronising it (a device kernel
+ * recounts the buckets' good nodes); ordering them against _dev calls issued on other streams is
+ * the caller's business, as with the accept setters. */
+int dhtgpu_rt_set_good(dhtgpu_ctx* ctx, const uint8_t* good);
+int dhtgpu_rt_update_good(dhtgpu_ctx* ctx, const uint32_t* idx, const uint8_t* val, uint32_t m);
+/* RoutingTable::findClosestNodes(target, now, count) (src/routing_table.cpp:110-150) for q targets
+ * over the resident table and its current good bits: the results of dhtgpu_find_closest --
+ * out_idx[q*count] indexes the uploaded nodes, DHTGPU_NONE padded, out_cnt[q]; 1 <= count <=
+ * DHTGPU_MAX_K.  One wave per target.  The _dev forms take target planes (t_planes[j*t_stride +
+ * i], any t_stride >= q) and device outputs, are stream-ordered (NULL = the context's stream)
+ * and neither synchronise nor allocate; an empty table gives out_cnt = 0 and DHTGPU_NONE rows.
+ * Every rt query returns DHTGPU_ENOIDS before the first dhtgpu_rt_set. */
+int dhtgpu_rt_find_closest_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_stride, uint32_t q,
+                               uint32_t count, uint32_t* out_idx, uint32_t* out_cnt, void* stream);
+int dhtgpu_rt_find_closest(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, uint32_t count,
+                           uint32_t* out_idx, uint32_t* out_cnt);
+/* The find_node / get reply (Dht::onFindNode, src/dht.cpp:2128-2138; onGetValues, :2141-2161): per
+ * target, findClosestNodes(target, now, TARGET_NODES = 8) written as NetworkEngine::bufferNodes
+ * (src/network_engine.cpp:1003-1032) writes it -- 26-byte (af 4) / 38-byte (af 6) records at
+ * out[qi * 8 * rec ..], out_len[qi] bytes of them (the bytes past out_len[qi] are unspecified).
+ * Byte-identical to dhtgpu_rt_find_closest_dev at count 8 followed by dhtgpu_buffer_nodes_ids
+ * over the same nodes.  out_idx[q*8] (nullable) also receives the indices. */
+int dhtgpu_rt_reply_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_stride, uint32_t q, uint8_t* out,
+                        uint32_t* out_len, uint32_t* out_idx, void* stream);
+int dhtgpu_rt_reply(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, uint8_t* out, uint32_t* out_len,
+                    uint32_t* out_idx);
+/* The closeness test after findClosestNodes: out_flag[qi] = 1 iff the count-node result holds at
+ * least max(min_nodes, 1) nodes and target.xorCmp(last result's id, myid) < 0
+ * (include/opendht/infohash.h:179-194), else 0 -- a last node equal to myid gives 0.  count = 8,
+ * min_nodes = 1 is Dht::maintainStorage's test when not forced (src/dht.cpp:1862-1879); count =
+ * 14, min_nodes = 8 is Dht::onAnnounce's drop test (:2293-2294).  out_flag: u8[q]; out_cnt[q]
+ * (nullable) = the result sizes. */
+int dhtgpu_rt_closer_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_stride, uint32_t q, uint32_t count,
+                         uint32_t min_nodes, uint8_t* out_flag, uint32_t* out_cnt, void* stream);
+int dhtgpu_rt_closer(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, uint32_t count, uint32_t min_nodes,
+                     uint8_t* out_flag, uint32_t* out_cnt);
 
 /* ---- K2: routing-bucket classification over the context's id set -------------- */
 /* out_bucket[n] (nullable) = findBucket(id) index; hist161[161] = histogram of

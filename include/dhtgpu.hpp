@@ -13,6 +13,11 @@
  *       set: std::partial_sort(.., InfoHash::xorCmp) (include/opendht/infohash.h:179-194)
  *   bufferNodesBatch(ctx, af6, targets, nodes)             <- NetworkEngine::bufferNodes
  *       (src/network_engine.cpp:1003-1032), batched
+ *   ResidentTable                                          the RoutingTable kept on the device:
+ *       replyNodesBatch      <- Dht::onFindNode / onGetValues (src/dht.cpp:2128-2161):
+ *                               findClosestNodes(target, now, 8) + bufferNodes, fused
+ *       closerThanSelfBatch  <- the closeness tests of Dht::maintainStorage (src/dht.cpp:1862-1879)
+ *                               and Dht::onAnnounce (:2293-2294)
  *
  * The templates are written against the reference's member names only -- a table is a
  * list of buckets with `.first` (InfoHash) and `.nodes` (list of Sp<Node>); a node has
@@ -29,7 +34,9 @@
  * the helpers answer on the host -- the same walk as the reference body -- below
  * Context::min_device_batch targets (default kMinDeviceBatch = 1024, above the measured
  * crossover of ~740) and only larger batches go to the device.  A single call is therefore
- * as fast as the reference's own (tests/cpp/adapter_check.cpp reports both).
+ * as fast as the reference's own (tests/cpp/adapter_check.cpp reports both).  ResidentTable
+ * keeps the table on the device, which halves the fixed cost; its thresholds (kMinResidentBatch,
+ * kMinResidentReplyBatch) are lower accordingly.
  */
 #ifndef DHTGPU_HPP
 #define DHTGPU_HPP
@@ -86,6 +93,28 @@ template <class H>
 inline void put_id(std::vector<uint8_t>& out, const H& h) {
     const uint8_t* p = h.data();
     out.insert(out.end(), p, p + DHTGPU_HASH_LEN);
+}
+
+/* a node's address || port bytes as its sockaddr holds them (network order): the tail of a
+ * bufferNodes record (src/network_engine.cpp:1016-1027) */
+template <class NodeT>
+inline void put_tail(std::vector<uint8_t>& out, const NodeT& nd, bool af_inet6) {
+    const uint8_t* a;
+    const uint8_t* p;
+    size_t alen;
+    if (af_inet6) {
+        const auto& sin6 = nd.getAddr().getIPv6();
+        a = reinterpret_cast<const uint8_t*>(&sin6.sin6_addr);
+        p = reinterpret_cast<const uint8_t*>(&sin6.sin6_port);
+        alen = 16;
+    } else {
+        const auto& sin = nd.getAddr().getIPv4();
+        a = reinterpret_cast<const uint8_t*>(&sin.sin_addr);
+        p = reinterpret_cast<const uint8_t*>(&sin.sin_port);
+        alen = 4;
+    }
+    out.insert(out.end(), a, a + alen);
+    out.insert(out.end(), p, p + 2);
 }
 
 /* InfoHash::xorCmp(a, b) < 0 for target t (include/opendht/infohash.h:179-194): at the first
@@ -155,6 +184,32 @@ cached_nodes_host(const NodeMap& c, const HashT& id, size_t count) {
             if (!n->isExpired() && !n->isClient()) res.push_back(n);
     }
     return res;
+}
+/* The find_node / get reply on the host: findClosestNodes(id, now, 8) (already in xorCmp order,
+ * so bufferNodes' sort keeps it) packed as id || address || port records. */
+template <class Table, class HashT, class TimePoint>
+std::vector<uint8_t> reply_nodes_host(const Table& table, const HashT& id, TimePoint now, bool af_inet6) {
+    typedef typename std::decay<decltype(*table.begin()->nodes.begin())>::type NodePtr;
+    std::vector<NodePtr> nodes;
+    find_closest_host(table, id, now, 8, nodes);
+    std::vector<uint8_t> out;
+    out.reserve(nodes.size() * (af_inet6 ? 38 : 26));
+    for (const auto& n : nodes) {
+        put_id(out, n->id);
+        put_tail(out, *n, af_inet6);
+    }
+    return out;
+}
+
+/* findClosestNodes(id, now, count) holds at least max(min_nodes, 1) nodes and
+ * id.xorCmp(nodes.back()->id, myid) < 0 (src/dht.cpp:1862-1879, :2293-2294). */
+template <class Table, class HashT, class TimePoint>
+bool closer_than_self_host(const Table& table, const HashT& id, TimePoint now, size_t count, size_t min_nodes,
+                           const uint8_t* myid) {
+    typedef typename std::decay<decltype(*table.begin()->nodes.begin())>::type NodePtr;
+    std::vector<NodePtr> nodes;
+    find_closest_host(table, id, now, count, nodes);
+    return nodes.size() >= (min_nodes ? min_nodes : 1) && xor_closer(id.data(), nodes.back()->id.data(), myid);
 }
 }  // namespace detail
 
@@ -353,6 +408,146 @@ public:
     }
 private:
     Context& ctx_;
+};
+
+/* The routing table resident on the device (dhtgpu_rt_*): the responder path.  Wiring:
+ *   assign(table, af, version)   when the table changes (a node added or removed, a bucket
+ *                                split): the snapshot rule of TableSnapshot plus every node's
+ *                                address || port (af 4 / 6; 0 = no tails, no replies); a version
+ *                                != 0 equal to the last one's skips the upload
+ *   refresh(table, now)          once per batch: the isGood(now) bits only
+ *   findClosestNodesBatch / replyNodesBatch / closerThanSelfBatch   the batch itself
+ * Batches below min_device_batch (replies: min_reply_batch) targets never touch the device: they
+ * run the reference's walk on the table they are given (detail::find_closest_host) and, for replies, pack the records on
+ * the host -- neither assign nor refresh is needed for them.  Larger batches answer from the
+ * mirror, i.e. from the table as last assigned and refreshed. */
+/* Smallest batches answered from the mirror, from the measured crossovers of DESIGN.md §5j
+ * (profiles/r10/rtable/rtable_check_run.txt: refresh + the batch call against the host walk, both
+ * through this adapter; fixed cost / (host - device cost per target)): replies 59.6 us / (0.250 -
+ * 0.051) us = 299 targets; node lists 51.6 us / (0.183 - 0.108) us = 688 -- both paths build the
+ * same vectors of node pointers, which is most of either side's cost per target.  The closeness
+ * flags were not measured and follow the node lists' threshold. */
+static const size_t kMinResidentBatch = 768;
+static const size_t kMinResidentReplyBatch = 320;
+
+template <class Table, class TimePoint>
+class ResidentTable {
+public:
+    typedef typename TableSnapshot<Table, TimePoint>::NodePtr NodePtr;
+    template <class HashT>
+    ResidentTable(Context& ctx, const HashT& myid)
+        : min_device_batch(kMinResidentBatch), min_reply_batch(kMinResidentReplyBatch), ctx_(ctx), alen_(0) {
+        std::memcpy(myid_, myid.data(), DHTGPU_HASH_LEN);
+    }
+    size_t min_device_batch;   // smallest batch answered from the mirror: node lists and closeness flags
+    size_t min_reply_batch;    // ... replies
+
+    void assign(const Table& table, unsigned af, uint64_t version = 0) {
+        if (af != 0 && af != 4 && af != 6) throw Error(DHTGPU_EINVAL, "ResidentTable::assign: af");
+        alen_ = af == 4 ? 4u : af == 6 ? 16u : 0u;
+        std::vector<uint8_t> firsts, ids, tail;
+        std::vector<uint32_t> off;
+        nodes_.clear();
+        for (const auto& b : table) {
+            detail::put_id(firsts, b.first);
+            off.push_back((uint32_t)nodes_.size());
+            for (const auto& n : b.nodes) {
+                detail::put_id(ids, n->id);
+                if (alen_) detail::put_tail(tail, *n, af == 6);
+                nodes_.push_back(n);
+            }
+        }
+        off.push_back((uint32_t)nodes_.size());
+        static const uint8_t none[DHTGPU_HASH_LEN] = {0};
+        check(dhtgpu_rt_set(ctx_.get(), myid_, (uint32_t)(off.size() - 1), firsts.data(), off.data(),
+                            ids.empty() ? nullptr : ids.data(), alen_ ? (tail.empty() ? none : tail.data()) : nullptr,
+                            af, version),
+              "rt_set");
+    }
+
+    /* the isGood(now) bits of the assigned nodes, in the assigned order */
+    void refresh(const Table& table, TimePoint now) {
+        std::vector<uint8_t> good;
+        good.reserve(nodes_.size());
+        for (const auto& b : table)
+            for (const auto& n : b.nodes) good.push_back(n->isGood(now) ? 1 : 0);
+        if (good.size() != nodes_.size()) throw Error(DHTGPU_EINVAL, "ResidentTable::refresh: the table changed, assign it");
+        check(dhtgpu_rt_set_good(ctx_.get(), good.empty() ? nullptr : good.data()), "rt_set_good");
+    }
+
+    template <class HashT>
+    std::vector<std::vector<NodePtr>> findClosestNodesBatch(const Table& table, const HashT* targets, size_t q,
+                                                            TimePoint now, size_t count) const {
+        std::vector<std::vector<NodePtr>> res(q);
+        if (q == 0 || count == 0) return res;
+        if (host(q, count)) {
+            for (size_t i = 0; i < q; ++i) detail::find_closest_host(table, targets[i], now, count, res[i]);
+            return res;
+        }
+        const std::vector<uint8_t> t = pack(targets, q);
+        std::vector<uint32_t> idx(q * count), cnt(q);
+        check(dhtgpu_rt_find_closest(ctx_.get(), t.data(), (uint32_t)q, (uint32_t)count, idx.data(), cnt.data()),
+              "rt_find_closest");
+        for (size_t i = 0; i < q; ++i) {
+            res[i].reserve(cnt[i]);
+            for (uint32_t r = 0; r < cnt[i]; ++r) res[i].push_back(nodes_[idx[i * count + r]]);
+        }
+        return res;
+    }
+
+    /* the find_node / get reply per target: findClosestNodes(target, now, 8) as bufferNodes packs it */
+    template <class HashT>
+    std::vector<std::vector<uint8_t>> replyNodesBatch(const Table& table, const HashT* targets, size_t q,
+                                                      TimePoint now) const {
+        if (!alen_) throw Error(DHTGPU_EINVAL, "ResidentTable::replyNodesBatch: assigned without an address family");
+        const uint32_t rec = 20 + alen_ + 2;
+        std::vector<std::vector<uint8_t>> res(q);
+        if (q == 0) return res;
+        if (q < min_reply_batch) {
+            for (size_t i = 0; i < q; ++i) res[i] = detail::reply_nodes_host(table, targets[i], now, alen_ == 16);
+            return res;
+        }
+        const std::vector<uint8_t> t = pack(targets, q);
+        std::vector<uint8_t> out(q * 8 * rec);
+        std::vector<uint32_t> len(q);
+        check(dhtgpu_rt_reply(ctx_.get(), t.data(), (uint32_t)q, out.data(), len.data(), nullptr), "rt_reply");
+        for (size_t i = 0; i < q; ++i) res[i].assign(out.begin() + i * 8 * rec, out.begin() + i * 8 * rec + len[i]);
+        return res;
+    }
+
+    /* flag[i] = findClosestNodes(targets[i], now, count) holds at least max(min_nodes, 1) nodes and
+     * targets[i].xorCmp(nodes.back()->id, myid) < 0: (8, 1) is maintainStorage's test, (14, 8)
+     * onAnnounce's */
+    template <class HashT>
+    std::vector<uint8_t> closerThanSelfBatch(const Table& table, const HashT* targets, size_t q, TimePoint now,
+                                             size_t count, size_t min_nodes) const {
+        std::vector<uint8_t> flag(q, 0);
+        if (q == 0 || count == 0) return flag;
+        if (host(q, count)) {
+            for (size_t i = 0; i < q; ++i)
+                flag[i] = detail::closer_than_self_host(table, targets[i], now, count, min_nodes, myid_);
+            return flag;
+        }
+        const std::vector<uint8_t> t = pack(targets, q);
+        check(dhtgpu_rt_closer(ctx_.get(), t.data(), (uint32_t)q, (uint32_t)count, (uint32_t)min_nodes, flag.data(),
+                               nullptr),
+              "rt_closer");
+        return flag;
+    }
+
+private:
+    bool host(size_t q, size_t count) const { return q < min_device_batch || count > DHTGPU_MAX_K; }
+    template <class HashT>
+    static std::vector<uint8_t> pack(const HashT* targets, size_t q) {
+        std::vector<uint8_t> t;
+        t.reserve(q * DHTGPU_HASH_LEN);
+        for (size_t i = 0; i < q; ++i) detail::put_id(t, targets[i]);
+        return t;
+    }
+    Context& ctx_;
+    uint8_t myid_[DHTGPU_HASH_LEN];
+    uint32_t alen_;
+    std::vector<NodePtr> nodes_;
 };
 
 /* Drop-in for NetworkEngine::bufferNodes(af, id, nodes) (src/network_engine.cpp:1003-1032)

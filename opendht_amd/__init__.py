@@ -12,6 +12,8 @@ Reference interfaces mirrored (OpenDHT tree paths):
   Context.cached_nodes    NodeCache::getCachedNodes                 (src/node_cache.cpp:42-74)
   Context.cache_set/_nodes  the NodeCache mirror: unsorted keys sorted on the device (node_cache.h:43)
   Context.classify        RoutingTable::findBucket + InfoHash::commonBits
+  Context.rt_set / rt_reply / rt_closer  the routing table resident on the device: onFindNode / onGetValues'
+                          findClosestNodes + bufferNodes fused; maintainStorage / onAnnounce closeness tests
 """
 import ctypes
 import os
@@ -135,6 +137,19 @@ def lib():
                                  _u32p], ctypes.c_int),
         "dhtgpu_search_batch_dev": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp,
                                      _vp, _vp, _vp, _vp], ctypes.c_int),
+        "dhtgpu_rt_set": ([_vp, _u8p, ctypes.c_uint32, _u8p, _u32p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint64],
+                          ctypes.c_int),
+        "dhtgpu_rt_set_good": ([_vp, _u8p], ctypes.c_int),
+        "dhtgpu_rt_update_good": ([_vp, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_rt_find_closest_dev": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp],
+                                       ctypes.c_int),
+        "dhtgpu_rt_find_closest": ([_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_rt_reply_dev": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "dhtgpu_rt_reply": ([_vp, _u8p, ctypes.c_uint32, _u8p, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_rt_closer_dev": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                  _vp, _vp], ctypes.c_int),
+        "dhtgpu_rt_closer": ([_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u32p],
+                             ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("DHTGPU_LIB") and not hasattr(L, name):
@@ -161,7 +176,10 @@ def exported_symbols():
             "dhtgpu_sub_handles_active", "dhtgpu_handles_to_indices_dev", "dhtgpu_set_search_alpha", "dhtgpu_cache_set",
             "dhtgpu_cache_nodes", "dhtgpu_cache_sorted", "dhtgpu_buffer_nodes_ids", "dhtgpu_batch_events",
             "dhtgpu_search_insert", "dhtgpu_table_stats", "dhtgpu_set_accept", "dhtgpu_set_accept_bits_dev",
-            "dhtgpu_update_accept", "dhtgpu_num_accepted", "dhtgpu_write_ids", "dhtgpu_batch_plan"]
+            "dhtgpu_update_accept", "dhtgpu_num_accepted", "dhtgpu_write_ids", "dhtgpu_batch_plan",
+            "dhtgpu_rt_set", "dhtgpu_rt_set_good", "dhtgpu_rt_update_good", "dhtgpu_rt_find_closest_dev",
+            "dhtgpu_rt_find_closest", "dhtgpu_rt_reply_dev", "dhtgpu_rt_reply", "dhtgpu_rt_closer_dev",
+            "dhtgpu_rt_closer"]
 
 
 def _ids(a, name="ids"):
@@ -390,6 +408,86 @@ class Context:
                                          _p(nodes, _u8p), _p(good, _u8p), _p(t, _u8p), q, count,
                                          _p(out, _u32p), _p(cnt, _u32p)), "find_closest")
         return out, cnt
+
+    # ---- K1w: the resident routing table ------------------------------------------
+    def rt_set(self, myid, firsts, bucket_off, node_ids, node_tail=None, af=0, version=0):
+        """Upload a table snapshot (the arguments of find_closest) with myid and, optionally, the
+        nodes' address || port tails (af 4 / 6); every node starts good.  version != 0 equal to
+        the last upload's (same bucket and node counts) skips the upload."""
+        my = np.ascontiguousarray(myid, dtype=np.uint8).reshape(20)
+        firsts = _ids(firsts, "firsts") if len(firsts) else np.zeros((0, 20), np.uint8)
+        off = np.ascontiguousarray(bucket_off, dtype=np.uint32)
+        nodes = _ids(node_ids, "node_ids") if len(node_ids) else np.zeros((0, 20), np.uint8)
+        tail = None
+        if node_tail is not None:
+            tail = np.ascontiguousarray(node_tail, dtype=np.uint8).reshape(-1, (4 if af == 4 else 16) + 2)
+            if tail.shape[0] != nodes.shape[0]:
+                raise ValueError("node_tail must have one row per node")
+            if tail.shape[0] == 0:
+                tail = np.zeros((1, tail.shape[1]), np.uint8)
+        _check(lib().dhtgpu_rt_set(self._h, _p(my, _u8p), firsts.shape[0], _p(firsts, _u8p), _p(off, _u32p),
+                                   _p(nodes, _u8p), _p(tail, _u8p) if tail is not None else None, af, int(version)),
+               "rt_set")
+        self._rt = (nodes.shape[0], 0 if tail is None else tail.shape[1])
+
+    def rt_set_good(self, good):
+        """The Node::isGood(now) snapshot: (nn,) bool/uint8, nonzero = good."""
+        g = np.ascontiguousarray(np.asarray(good).reshape(-1) != 0, dtype=np.uint8)
+        if g.shape[0] != getattr(self, "_rt", (g.shape[0], 0))[0]:
+            raise ValueError("good must have one byte per node")
+        _check(lib().dhtgpu_rt_set_good(self._h, _p(g, _u8p) if g.size else None), "rt_set_good")
+
+    def rt_update_good(self, idx, val):
+        """good[idx[j]] = val[j] (val: array or one value for all)."""
+        i = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(val), i.shape)).astype(np.uint8).reshape(-1)
+        _check(lib().dhtgpu_rt_update_good(self._h, _p(i, _u32p), _p(v, _u8p), i.shape[0]), "rt_update_good")
+
+    def rt_find_closest(self, targets, count=8):
+        """find_closest over the resident table: (q, count) indices (NONE padded), (q,) counts."""
+        t = _ids(targets, "targets")
+        q = t.shape[0]
+        out = np.empty((q, count), dtype=np.uint32)
+        cnt = np.empty(q, dtype=np.uint32)
+        _check(lib().dhtgpu_rt_find_closest(self._h, _p(t, _u8p), q, count, _p(out, _u32p), _p(cnt, _u32p)),
+               "rt_find_closest")
+        return out, cnt
+
+    def rt_reply(self, targets, indices=False):
+        """The find_node reply per target: (q, 8*rec) uint8 blobs (bytes past the length
+        unspecified) and (q,) byte lengths; with indices=True also the (q, 8) node indices."""
+        t = _ids(targets, "targets")
+        q = t.shape[0]
+        rec = 20 + getattr(self, "_rt", (0, 6))[1]
+        out = np.zeros((q, 8 * rec), dtype=np.uint8)
+        ln = np.zeros(q, dtype=np.uint32)
+        idx = np.empty((q, 8), dtype=np.uint32) if indices else None
+        _check(lib().dhtgpu_rt_reply(self._h, _p(t, _u8p), q, _p(out, _u8p), _p(ln, _u32p),
+                                     _p(idx, _u32p) if indices else None), "rt_reply")
+        return (out, ln, idx) if indices else (out, ln)
+
+    def rt_closer(self, targets, count=8, min_nodes=1):
+        """The closeness test: (q,) uint8 flags -- the count-node result holds >= max(min_nodes, 1)
+        nodes and its last node is closer to the target than myid -- and (q,) result sizes."""
+        t = _ids(targets, "targets")
+        q = t.shape[0]
+        flag = np.empty(q, dtype=np.uint8)
+        cnt = np.empty(q, dtype=np.uint32)
+        _check(lib().dhtgpu_rt_closer(self._h, _p(t, _u8p), q, count, min_nodes, _p(flag, _u8p), _p(cnt, _u32p)),
+               "rt_closer")
+        return flag, cnt
+
+    def rt_find_closest_dev(self, t_planes_ptr, t_stride, q, count, out_idx_ptr, out_cnt_ptr, stream=None):
+        _check(lib().dhtgpu_rt_find_closest_dev(self._h, t_planes_ptr, t_stride, q, count, out_idx_ptr, out_cnt_ptr,
+                                                stream), "rt_find_closest_dev")
+
+    def rt_reply_dev(self, t_planes_ptr, t_stride, q, out_ptr, out_len_ptr, out_idx_ptr=None, stream=None):
+        _check(lib().dhtgpu_rt_reply_dev(self._h, t_planes_ptr, t_stride, q, out_ptr, out_len_ptr, out_idx_ptr,
+                                         stream), "rt_reply_dev")
+
+    def rt_closer_dev(self, t_planes_ptr, t_stride, q, count, min_nodes, out_flag_ptr, out_cnt_ptr=None, stream=None):
+        _check(lib().dhtgpu_rt_closer_dev(self._h, t_planes_ptr, t_stride, q, count, min_nodes, out_flag_ptr,
+                                          out_cnt_ptr, stream), "rt_closer_dev")
 
     # ---- a11 / f4: compact node wire format ---------------------------------------
     def buffer_nodes(self, node_tail, af, targets, cand):

@@ -7,7 +7,7 @@
 // everything in order and an early return leaks nothing.
 // Layout: owners and the context; helpers shared by several entry points (each sequence stands
 // once); then the entry points by family -- id set, accept mask, K1, K4, K6, table, caches,
-// wire format, searches, crawl model.
+// wire format, searches, the resident routing table, crawl model.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
@@ -245,6 +245,17 @@ struct dhtgpu_ctx {
     uint64_t cache_version = 0;
     DevBuf cache_in, sort_scratch, cache_acc;
     DevBuf srch;            // search_insert / table_stats staging
+    // Resident routing table (dhtgpu_rt_set ...): one blob -- firsts planes | off | good prefix
+    // sums | myid | node planes | good bytes | tails -- and the kernels' view of it.  Private to
+    // the rt entry points: the k-NN id set, the accept mask and the cache mirror know nothing of it.
+    struct RTable {
+        DevBuf buf;
+        RtView v = {};
+        uint32_t* gpre = nullptr;   // v.gpre / v.good, writable (the good setters)
+        uint8_t* good = nullptr;
+        bool valid = false;
+        uint64_t version = 0;
+    } rt;
     // diagnostics: DHTGPU_DBG, the library's one diagnostics switch, read once at creation and
     // masked to kDbgAllowed -- bit 256: per-block phase stamps of F2 / F3 printed to stderr;
     // bit 2^23: K6 instead of KS for batches of <= 64 targets (both exact).  Neither changes a
@@ -478,6 +489,28 @@ static int host_topk(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, 
     if (int r = run(c->targets.as<uint32_t>(), ts, c->aux2.as<uint32_t>(), c->aux3.as<uint32_t>())) return r;
     DHT_TRY(hipMemcpyAsync(out_idx, c->aux2.p, (size_t)q * k * 4, hipMemcpyDeviceToHost, c->stream));
     DHT_TRY(hipMemcpyAsync(out_cnt, c->aux3.p, (size_t)q * 4, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    return DHTGPU_OK;
+}
+
+// The same sequence for entry points whose results are not index rows: N device blocks carved out
+// of aux2, filled by run(tp, ts, p) on the context's stream and copied to the host pointers that
+// are set (a null one names an output the caller did not ask for).
+struct HostOut {
+    void* host;
+    size_t bytes;
+};
+template <size_t N, class Run>
+static int host_rows(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, const HostOut (&o)[N], Run run) {
+    uint64_t ts = 0;
+    DHT_TRY(c->upload_targets(t20, q, &ts));
+    size_t sz[N];
+    uint8_t* p[N];
+    for (size_t i = 0; i < N; ++i) sz[i] = o[i].bytes;
+    DHT_TRY(carve(c->aux2, sz, p));
+    if (int r = run(c->targets.as<uint32_t>(), ts, p)) return r;
+    for (size_t i = 0; i < N; ++i)
+        if (o[i].host) DHT_TRY(hipMemcpyAsync(o[i].host, p[i], sz[i], hipMemcpyDeviceToHost, c->stream));
     DHT_TRY(hipStreamSynchronize(c->stream));
     return DHTGPU_OK;
 }
@@ -1812,6 +1845,147 @@ int dhtgpu_table_stats(dhtgpu_ctx* c, uint32_t nb, const uint8_t* firsts20, int3
     DHT_TRY(hipMemcpyAsync(out_depth, base + a + bsz, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
     DHT_TRY(hipStreamSynchronize(c->stream));
     return DHTGPU_OK;
+}
+
+// ---- K1w: the resident routing table ---------------------------------------------------------
+int dhtgpu_rt_set(dhtgpu_ctx* c, const uint8_t* myid20, uint32_t nb, const uint8_t* firsts20, const uint32_t* off,
+                  const uint8_t* node_ids20, const uint8_t* node_tail, uint32_t af, uint64_t version) {
+    if (!c || !myid20 || nb > 256 || (nb && (!firsts20 || !off))) return DHTGPU_EINVAL;
+    if (node_tail ? (af != 4 && af != 6) : af != 0) return DHTGPU_EINVAL;
+    for (uint32_t b = 0; b < nb; ++b)
+        if (off[b] > off[b + 1]) return DHTGPU_EINVAL;
+    const uint32_t nn = nb ? off[nb] : 0;
+    if (nn && !node_ids20) return DHTGPU_EINVAL;
+    dhtgpu_ctx::RTable& t = c->rt;
+    if (version && t.valid && version == t.version && nb == t.v.nb && nn == t.v.nn) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    t.valid = false;
+    t.version = 0;
+    const uint64_t ns = pad_q(nn ? nn : 1);
+    const uint32_t alen = af == 4 ? 4u : af == 6 ? 16u : 0u;
+    const std::vector<uint32_t> fp = firsts_planes(firsts20, nb);
+    uint32_t my[5];
+    for (int w = 0; w < 5; ++w) my[w] = be32(myid20 + 4 * w);
+    const uint32_t zero = 0;
+    const size_t sz[] = {fp.size() * 4, (size_t)(nb + 1) * 4, (size_t)(nb + 1) * 4, sizeof my,
+                         (size_t)ns * 5 * 4, (size_t)ns, (size_t)nn * (alen + 2)};
+    uint8_t* p[7];
+    DHT_TRY(carve(t.buf, sz, p));
+    if (nb) DHT_TRY(hipMemcpyAsync(p[0], fp.data(), sz[0], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(hipMemcpyAsync(p[1], nb ? off : &zero, sz[1], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(hipMemcpyAsync(p[3], my, sizeof my, hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(hipMemsetAsync(p[5], 0, (size_t)ns, c->stream));
+    if (nn) DHT_TRY(hipMemsetAsync(p[5], 1, nn, c->stream));   // every node starts good
+    if (alen && nn) DHT_TRY(hipMemcpyAsync(p[6], node_tail, sz[6], hipMemcpyHostToDevice, c->stream));
+    if (int r = upload_ids(c, node_ids20, nn, reinterpret_cast<uint32_t*>(p[4]), ns)) return r;
+    t.gpre = reinterpret_cast<uint32_t*>(p[2]);
+    t.good = p[5];
+    t.v = RtView{nb, nn, reinterpret_cast<const uint32_t*>(p[0]), reinterpret_cast<const uint32_t*>(p[1]), t.gpre,
+                 reinterpret_cast<const uint32_t*>(p[4]), ns, t.good, alen ? p[6] : nullptr, alen,
+                 reinterpret_cast<const uint32_t*>(p[3])};
+    DHT_TRY(launch_rt_gpre(t.v, t.gpre, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    t.version = version;
+    t.valid = true;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_rt_set_good(dhtgpu_ctx* c, const uint8_t* good) {
+    if (!c) return DHTGPU_EINVAL;
+    if (!c->rt.valid) return DHTGPU_ENOIDS;
+    if (!c->rt.v.nn) return DHTGPU_OK;
+    if (!good) return DHTGPU_EINVAL;
+    DHT_TRY(c->bind());
+    DHT_TRY(hipMemcpyAsync(c->rt.good, good, c->rt.v.nn, hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(launch_rt_gpre(c->rt.v, c->rt.gpre, c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_rt_update_good(dhtgpu_ctx* c, const uint32_t* idx, const uint8_t* val, uint32_t m) {
+    if (!c || (m && (!idx || !val))) return DHTGPU_EINVAL;
+    if (!c->rt.valid) return DHTGPU_ENOIDS;
+    for (uint32_t j = 0; j < m; ++j)
+        if (idx[j] >= c->rt.v.nn) return DHTGPU_EINVAL;   // nothing applied
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const size_t ib = al256((size_t)m * 4);
+    DHT_TRY(c->staging.ensure(ib + (size_t)m));
+    DHT_TRY(hipMemcpyAsync(c->staging.p, idx, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(hipMemcpyAsync(c->staging.as<uint8_t>() + ib, val, (size_t)m, hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(launch_rt_good_set(c->rt.good, c->staging.as<uint32_t>(), c->staging.as<uint8_t>() + ib, m, c->stream));
+    DHT_TRY(launch_rt_gpre(c->rt.v, c->rt.gpre, c->stream));
+    return DHTGPU_OK;
+}
+
+// Argument checks shared by the rt query entry points (tp: the targets, device planes or host bytes).
+static int check_rt(const dhtgpu_ctx* c, const void* tp, uint32_t q, uint32_t count, bool outs) {
+    if (!c || count == 0 || count > DHTGPU_MAX_K || (q && (!tp || !outs))) return DHTGPU_EINVAL;
+    if (!c->rt.valid) return DHTGPU_ENOIDS;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_rt_find_closest_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t count,
+                               uint32_t* out_idx, uint32_t* out_cnt, void* stream) {
+    if (int r = check_rt(c, tp, q, count, out_idx && out_cnt)) return r;
+    if (!q) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_rt_find(c->rt.v, tp, ts, q, count, out_idx, out_cnt, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_rt_reply_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint8_t* out, uint32_t* out_len,
+                        uint32_t* out_idx, void* stream) {
+    if (int r = check_rt(c, tp, q, 8, out && out_len)) return r;
+    if (!c->rt.v.tail) return DHTGPU_EINVAL;   // set without tails
+    if (!q) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_rt_reply(c->rt.v, tp, ts, q, out, out_len, out_idx, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_rt_closer_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t count, uint32_t min_nodes,
+                         uint8_t* out_flag, uint32_t* out_cnt, void* stream) {
+    if (int r = check_rt(c, tp, q, count, out_flag != nullptr)) return r;
+    if (!q) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_rt_closer(c->rt.v, tp, ts, q, count, min_nodes, out_flag, out_cnt, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_rt_find_closest(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t count, uint32_t* out_idx,
+                           uint32_t* out_cnt) {
+    if (int r = check_rt(c, t20, q, count, out_idx && out_cnt)) return r;
+    if (!q) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    return host_topk(c, t20, q, count, out_idx, out_cnt,
+                     [&](const uint32_t* tp, uint64_t ts, uint32_t* d_idx, uint32_t* d_cnt) {
+        return dhtgpu_rt_find_closest_dev(c, tp, ts, q, count, d_idx, d_cnt, c->stream);
+    });
+}
+
+int dhtgpu_rt_reply(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint8_t* out, uint32_t* out_len, uint32_t* out_idx) {
+    if (int r = check_rt(c, t20, q, 8, out && out_len)) return r;
+    if (!c->rt.v.tail) return DHTGPU_EINVAL;
+    if (!q) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const HostOut o[] = {{out, (size_t)q * 8 * (20 + c->rt.v.alen + 2)}, {out_len, (size_t)q * 4},
+                         {out_idx, (size_t)q * 8 * 4}};
+    return host_rows(c, t20, q, o, [&](const uint32_t* tp, uint64_t ts, uint8_t* const* p) {
+        return dhtgpu_rt_reply_dev(c, tp, ts, q, p[0], reinterpret_cast<uint32_t*>(p[1]),
+                                   out_idx ? reinterpret_cast<uint32_t*>(p[2]) : nullptr, c->stream);
+    });
+}
+
+int dhtgpu_rt_closer(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t count, uint32_t min_nodes,
+                     uint8_t* out_flag, uint32_t* out_cnt) {
+    if (int r = check_rt(c, t20, q, count, out_flag != nullptr)) return r;
+    if (!q) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const HostOut o[] = {{out_flag, (size_t)q}, {out_cnt, (size_t)q * 4}};
+    return host_rows(c, t20, q, o, [&](const uint32_t* tp, uint64_t ts, uint8_t* const* p) {
+        return dhtgpu_rt_closer_dev(c, tp, ts, q, count, min_nodes, p[0],
+                                    out_cnt ? reinterpret_cast<uint32_t*>(p[1]) : nullptr, c->stream);
+    });
 }
 
 // ---- f3: crawl replay (iterative searches over a synthetic network) ----------------------

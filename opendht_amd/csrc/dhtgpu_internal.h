@@ -232,6 +232,34 @@ hipError_t launch_wire_decode(const uint8_t* blob, const uint64_t* msg_off, cons
                               const uint8_t* from_addr, uint8_t* out_ids, uint8_t* out_tail, uint8_t* out_status,
                               hipStream_t s);
 
+// rtable.hip: K1w, the resident routing table (dhtgpu_rt_*).  The mirror as the kernels read it:
+// device pointers into one blob owned by the context.
+struct RtView {
+    uint32_t nb, nn;           // buckets (<= 256), nodes (= off[nb])
+    const uint32_t* fp;        // bucket firsts as word planes: fp[w * nb + b]
+    const uint32_t* off;       // [nb + 1] bucket b owns nodes [off[b], off[b + 1])
+    const uint32_t* gpre;      // [nb + 1] good nodes of buckets [0, b)
+    const uint32_t* np;        // node word planes, np[w * ns + i]
+    uint64_t ns;
+    const uint8_t* good;       // [nn] Node::isGood(now)
+    const uint8_t* tail;       // [nn * (alen + 2)] address || port (null: set without tails)
+    uint32_t alen;             // 4 / 16 (0 without tails)
+    const uint32_t* myid;      // 5 words
+};
+// gpre from off and good (one workgroup; after every change of the good bytes)
+hipError_t launch_rt_gpre(const RtView& v, uint32_t* gpre, hipStream_t s);
+// good[idx[j]] = val[j] != 0, j < m (device arrays; idx < nn checked by the caller)
+hipError_t launch_rt_good_set(uint8_t* good, const uint32_t* idx, const uint8_t* val, uint32_t m, hipStream_t s);
+// findClosestNodes per target over the mirror (1 <= count <= DHTGPU_MAX_K_DEV): indices + counts;
+// the count-8 result as bufferNodes records (out_idx nullable: q x 8); the closeness flag
+// (out_cnt nullable)
+hipError_t launch_rt_find(const RtView& v, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t count,
+                          uint32_t* out_idx, uint32_t* out_cnt, hipStream_t s);
+hipError_t launch_rt_reply(const RtView& v, const uint32_t* tp, uint64_t ts, uint32_t q, uint8_t* out,
+                           uint32_t* out_len, uint32_t* out_idx, hipStream_t s);
+hipError_t launch_rt_closer(const RtView& v, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t count,
+                            uint32_t min_nodes, uint8_t* out_flag, uint32_t* out_cnt, hipStream_t s);
+
 // crawl.hip: crawl-replay model (iterative searches over implicit routing tables)
 uint32_t search_list_cap();
 // sorts the K4 index buckets (index workspace, n ids, B bits) by (w0, index) into out[n]
