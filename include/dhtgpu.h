@@ -32,6 +32,9 @@
  *                          findClosestNodes(target, now, TARGET_NODES) + bufferNodes, fused
  *   dhtgpu_rt_closer       the closeness tests of Dht::maintainStorage (src/dht.cpp:1862-1879) and
  *                          Dht::onAnnounce (:2293-2294): findClosestNodes + xorCmp(nodes.back(), myid)
+ *   dhtgpu_nc_set/_insert/_erase  NodeCache's map (node_cache.h:43) resident on the device, changed
+ *                          incrementally (NodeMap::getNode, clearBadNodes: src/node_cache.cpp:87-123)
+ *   dhtgpu_nc_nodes        NodeCache::getCachedNodes (src/node_cache.cpp:42-74) over it, one wave per target
  *
  * Threading (mirrors the reference, src/dhtrunner.cpp:115-150): one context per
  * thread, or external locking; every host-pointer call is synchronous.
@@ -362,6 +365,61 @@ int dhtgpu_rt_closer_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_s
                          uint32_t min_nodes, uint8_t* out_flag, uint32_t* out_cnt, void* stream);
 int dhtgpu_rt_closer(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, uint32_t count, uint32_t min_nodes,
                      uint8_t* out_flag, uint32_t* out_cnt);
+
+/* ---- K8w: the resident NodeCache ------------------------------------------------------------- */
+/* NodeCache::NodeMap (include/opendht/node_cache.h:43: std::map<InfoHash, weak_ptr<Node>>) kept on
+ * the device between calls and changed incrementally, so that a key heard of or dropped costs one
+ * pass over the resident keys instead of an upload and a sort of the whole map, and
+ * getCachedNodes (src/node_cache.cpp:42-74) crosses PCIe with its targets only.  One mirror per
+ * context, private to the nc entry points: the k-NN id set, its accept mask, the dhtgpu_cache_*
+ * mirror and the rt table are not touched, nor do they touch it.
+ *
+ * A key carries a HANDLE, the map's value: a u32 of the caller's choosing below
+ * DHTGPU_NC_MAX_HANDLE (its slot number for the weak_ptr<Node>); a handle at or over the bound is
+ * DHTGPU_EINVAL and nothing is applied; keeping handles unique is the caller's business.  The
+ * ACCEPT bitmask is indexed by handle: a bit is 1 where lock() && !isExpired() && !isClient()
+ * holds (src/node_cache.cpp:68-69).  It grows with the handles it is given (32 MB at the bound).
+ *
+ * dhtgpu_nc_set replaces the mirror with n keys in any order (sorted on the device; handles ==
+ * NULL: key i has handle i); every handle given starts accepted, every other bit is cleared.
+ * Duplicate keys return DHTGPU_EUNSORTED and leave the mirror invalid, as dhtgpu_cache_set does.
+ * n == 0 is a valid, empty mirror. */
+#define DHTGPU_NC_MAX_HANDLE (1u << 28)
+int dhtgpu_nc_set(dhtgpu_ctx* ctx, const uint8_t* ids20, const uint32_t* handles, uint64_t n);
+/* std::map::emplace (NodeMap::getNode, src/node_cache.cpp:99-111) for m keys, applied in batch
+ * order: a key already in the map keeps its handle and its accept bit, of equal keys in the batch
+ * the first wins; out_new[j] (nullable) = 1 where key j was inserted.  accept[m] (nullable: the
+ * new keys are accepted) sets the accept bit of each inserted key's handle.  DHTGPU_ERANGE when
+ * n + m >= 2^32 - 1.  dhtgpu_nc_erase is map.erase(key) (NodeMap::getNode(id) :87-97,
+ * clearBadNodes :113-123) for m keys in batch order: out_found[j] (nullable) = 1 where key j was
+ * erased -- 0 for an absent key and for a repeat of an earlier key of the batch; the handles' accept
+ * bits are left as they are.  Both are synchronous (the new size comes back) and run one pass over
+ * the resident keys, from one buffer set into the other, with geometric head-room; like
+ * dhtgpu_rt_set they must not be issued while nc lookups are in flight. */
+int dhtgpu_nc_insert(dhtgpu_ctx* ctx, const uint8_t* ids20, const uint32_t* handles, const uint8_t* accept,
+                     uint32_t m, uint8_t* out_new);
+int dhtgpu_nc_erase(dhtgpu_ctx* ctx, const uint8_t* ids20, uint32_t m, uint8_t* out_found);
+/* The accept bits: bit handles[j] = val[j] != 0 for m handles (distinct; host arrays) /
+ * bit h = accept_by_handle[h] != 0 for h < nh, the bits from nh on unchanged.  Both run on the
+ * context's stream without synchronising it, like dhtgpu_rt_update_good / dhtgpu_rt_set_good;
+ * handles past the mask's extent grow it (new bits are 0). */
+int dhtgpu_nc_update_accept(dhtgpu_ctx* ctx, const uint32_t* handles, const uint8_t* val, uint32_t m);
+int dhtgpu_nc_set_accept(dhtgpu_ctx* ctx, const uint8_t* accept_by_handle, uint32_t nh);
+/* *out_n = the number of keys; the keys (out_ids20[n*20]) and their handles (out_handles[n]) in
+ * lexicographic order, either nullable (tests; re-syncing an adapter). */
+int dhtgpu_nc_size(dhtgpu_ctx* ctx, uint64_t* out_n);
+int dhtgpu_nc_export(dhtgpu_ctx* ctx, uint8_t* out_ids20, uint32_t* out_handles);
+/* NodeCache::getCachedNodes(target, af, count) (src/node_cache.cpp:42-74) for q targets over the
+ * mirror and its current accept bits: out_handle[q*count] = the accepted keys' handles in the
+ * reference's walk order (lower_bound, then the XOR-closer of the two neighbours at every step --
+ * not sorted by distance), DHTGPU_NONE padded, out_cnt[q]; 1 <= count <= DHTGPU_MAX_K.  One wave
+ * per target.  The _dev form takes target planes (any t_stride >= q) and device outputs, is
+ * stream-ordered (NULL = the context's stream) and neither synchronises nor allocates.  Every nc
+ * query returns DHTGPU_ENOIDS before the first dhtgpu_nc_set. */
+int dhtgpu_nc_nodes_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_stride, uint32_t q, uint32_t count,
+                        uint32_t* out_handle, uint32_t* out_cnt, void* stream);
+int dhtgpu_nc_nodes(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, uint32_t count, uint32_t* out_handle,
+                    uint32_t* out_cnt);
 
 /* ---- K2: routing-bucket classification over the context's id set -------------- */
 /* out_bucket[n] (nullable) = findBucket(id) index; hist161[161] = histogram of

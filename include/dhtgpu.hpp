@@ -18,6 +18,9 @@
  *                               findClosestNodes(target, now, 8) + bufferNodes, fused
  *       closerThanSelfBatch  <- the closeness tests of Dht::maintainStorage (src/dht.cpp:1862-1879)
  *                               and Dht::onAnnounce (:2293-2294)
+ *   ResidentCache                                          NodeCache's map kept on the device and
+ *       changed incrementally (NodeMap::getNode / clearBadNodes, src/node_cache.cpp:87-123):
+ *       getCachedNodesBatch  <- NodeCache::getCachedNodes (src/node_cache.cpp:42-74)
  *
  * The templates are written against the reference's member names only -- a table is a
  * list of buckets with `.first` (InfoHash) and `.nodes` (list of Sp<Node>); a node has
@@ -46,6 +49,7 @@
 #include <cstdint>
 #include <cstring>
 #include <iterator>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -548,6 +552,215 @@ private:
     uint8_t myid_[DHTGPU_HASH_LEN];
     uint32_t alen_;
     std::vector<NodePtr> nodes_;
+};
+
+/* NodeCache's map resident on the device (dhtgpu_nc_*): the initiator path.  The adapter owns the
+ * handle space -- a slot vector of weak_ptr<Node> and a free list; a key's handle is its slot.
+ * Wiring:
+ *   assign(map)                 once (and to re-sync): the whole map, every slot's accept bit
+ *   noteInsert(id, node)        where NodeMap::getNode emplaces (src/node_cache.cpp:99-111); queued
+ *   noteErase(id)               where NodeMap::getNode(id) / clearBadNodes erase (:87-97, :113-123); queued
+ *   flush()                     the queue as one erase call and one insert call (a key inserted and
+ *                               erased again between two flushes never reaches the device)
+ *   refresh()                   once per batch: lock() && !isExpired() && !isClient() of every live
+ *                               slot (src/node_cache.cpp:68-69), as one mask upload
+ *   getCachedNodesBatch(map, targets, q, count)   the batch itself
+ * Batches below min_device_batch targets never touch the device: they run the reference's walk on
+ * the map they are given (detail::cached_nodes_host).  Larger batches flush the queue and answer
+ * from the mirror, i.e. with the accept bits of the last refresh; a node whose weak_ptr has
+ * expired since then is left out of its row. */
+/* Smallest batch answered from the mirror, from the crossover measured in DESIGN.md §5k
+ * (profiles/r11/ncache/ncache_check_run.txt: refresh + the batch call against the host walk, both
+ * through this adapter, 5,994 keys, count 8): the host walk wins at 256 targets (76.2 against 134.3
+ * us), the mirror at 512 (180.3 against 199.2 us); the two differences cross at 449 targets.
+ * kResidentCacheRebuildRatio: the queue length, as a fraction of the keys held, from which
+ * flush() rebuilds the mirror with dhtgpu_nc_set instead of one erase and one insert call
+ * (profiles/r11/ncache/nc_bench_large_m.json, 10^6 keys): an insert of 524,288 keys costs 1,248 us
+ * against 1,446 us for the rebuild, one of 10^6 keys 2,132 against 1,809 us; the differences cross
+ * at 705,000 keys.  The erase crosses at 789,000 keys. */
+static const size_t kMinResidentCacheBatch = 512;
+static const double kResidentCacheRebuildRatio = 0.705;
+
+/* ResidentCache's handle space, device-free: the slot vector, the free list, the keys held and
+ * the operations queued since the last flush. */
+template <class NodeT>
+class CacheSlots {
+public:
+    typedef std::shared_ptr<NodeT> NodePtr;
+    typedef std::weak_ptr<NodeT> NodeRef;
+    struct Key {
+        uint8_t b[DHTGPU_HASH_LEN];
+        bool operator<(const Key& o) const { return std::memcmp(b, o.b, DHTGPU_HASH_LEN) < 0; }
+    };
+    template <class HashT>
+    static Key key_of(const HashT& id) {
+        Key k;
+        std::memcpy(k.b, id.data(), DHTGPU_HASH_LEN);
+        return k;
+    }
+
+    void clear() {
+        slots_.clear();
+        free_.clear();
+        slot_of_.clear();
+        ins_.clear();
+        era_.clear();
+    }
+    /* std::map::emplace: a key already held keeps its slot; else the last freed slot, else a new one */
+    template <class HashT>
+    void noteInsert(const HashT& id, const NodeRef& node) {
+        const Key k = key_of(id);
+        if (slot_of_.count(k)) return;
+        uint32_t h;
+        if (!free_.empty()) {
+            h = free_.back();
+            free_.pop_back();
+            slots_[h] = node;
+        } else {
+            if (slots_.size() >= DHTGPU_NC_MAX_HANDLE) throw Error(DHTGPU_ERANGE, "ResidentCache: out of handles");
+            h = (uint32_t)slots_.size();
+            slots_.push_back(node);
+        }
+        slot_of_[k] = h;
+        ins_[k] = h;
+    }
+    /* map.erase(key): the slot goes to the free list; a queued insert of the key leaves the queue */
+    template <class HashT>
+    void noteErase(const HashT& id) {
+        const Key k = key_of(id);
+        const auto it = slot_of_.find(k);
+        if (it == slot_of_.end()) return;
+        slots_[it->second].reset();
+        free_.push_back(it->second);
+        slot_of_.erase(it);
+        if (!ins_.erase(k)) era_.push_back(k);   // (a key never sent needs no erase)
+    }
+    uint8_t accepted(uint32_t h) const {
+        const NodePtr n = slots_[h].lock();
+        return n && !n->isExpired() && !n->isClient() ? 1 : 0;
+    }
+    /* the slot of a key (DHTGPU_NONE: not held) */
+    template <class HashT>
+    uint32_t slotOf(const HashT& id) const {
+        const auto it = slot_of_.find(key_of(id));
+        return it == slot_of_.end() ? DHTGPU_NONE : it->second;
+    }
+    size_t size() const { return slot_of_.size(); }
+    size_t pending() const { return ins_.size() + era_.size(); }
+
+    std::vector<NodeRef> slots_;
+    std::vector<uint32_t> free_;
+    std::map<Key, uint32_t> slot_of_;   // the keys held (queued inserts included)
+    std::map<Key, uint32_t> ins_;       // queued inserts
+    std::vector<Key> era_;              // queued erases (keys the device holds)
+};
+
+template <class NodeMap>
+class ResidentCache {
+public:
+    typedef typename NodeMap::mapped_type::element_type NodeT;
+    typedef CacheSlots<NodeT> Slots;
+    typedef typename Slots::NodePtr NodePtr;
+    typedef typename Slots::NodeRef NodeRef;
+    typedef typename Slots::Key Key;
+    explicit ResidentCache(Context& ctx)
+        : min_device_batch(kMinResidentCacheBatch), rebuild_ratio(kResidentCacheRebuildRatio), ctx_(ctx) {}
+    size_t min_device_batch;   // smallest batch answered from the mirror
+    double rebuild_ratio;      // flush(): queued keys / keys held from which the mirror is rebuilt (0: never)
+
+    void assign(const NodeMap& map) {
+        s_.clear();
+        for (const auto& kv : map) {
+            s_.slot_of_[Slots::key_of(kv.first)] = (uint32_t)s_.slots_.size();
+            s_.slots_.push_back(kv.second);
+        }
+        rebuild();
+    }
+    template <class HashT>
+    void noteInsert(const HashT& id, const NodeRef& node) { s_.noteInsert(id, node); }
+    template <class HashT>
+    void noteErase(const HashT& id) { s_.noteErase(id); }
+
+    void flush() {
+        if (!s_.pending()) return;
+        if (rebuild_ratio > 0 && (double)s_.pending() >= rebuild_ratio * (double)s_.size()) {
+            s_.ins_.clear();
+            s_.era_.clear();
+            rebuild();
+            return;
+        }
+        if (!s_.era_.empty()) {
+            std::vector<uint8_t> ids;
+            ids.reserve(s_.era_.size() * DHTGPU_HASH_LEN);
+            for (const Key& k : s_.era_) ids.insert(ids.end(), k.b, k.b + DHTGPU_HASH_LEN);
+            check(dhtgpu_nc_erase(ctx_.get(), ids.data(), (uint32_t)s_.era_.size(), nullptr), "nc_erase");
+            s_.era_.clear();
+        }
+        if (!s_.ins_.empty()) {
+            std::vector<uint8_t> ids, acc;
+            std::vector<uint32_t> handles;
+            ids.reserve(s_.ins_.size() * DHTGPU_HASH_LEN);
+            for (const auto& kh : s_.ins_) {
+                ids.insert(ids.end(), kh.first.b, kh.first.b + DHTGPU_HASH_LEN);
+                handles.push_back(kh.second);
+                acc.push_back(s_.accepted(kh.second));
+            }
+            check(dhtgpu_nc_insert(ctx_.get(), ids.data(), handles.data(), acc.data(), (uint32_t)s_.ins_.size(), nullptr),
+                  "nc_insert");
+            s_.ins_.clear();
+        }
+    }
+
+    void refresh() {
+        if (s_.slots_.empty()) return;
+        std::vector<uint8_t> acc(s_.slots_.size());
+        for (size_t h = 0; h < acc.size(); ++h) acc[h] = s_.accepted((uint32_t)h);
+        check(dhtgpu_nc_set_accept(ctx_.get(), acc.data(), (uint32_t)acc.size()), "nc_set_accept");
+    }
+
+    template <class HashT>
+    std::vector<std::vector<NodePtr>> getCachedNodesBatch(const NodeMap& map, const HashT* targets, size_t q,
+                                                          size_t count) {
+        std::vector<std::vector<NodePtr>> res(q);
+        if (q == 0 || count == 0) return res;
+        if (q < min_device_batch || count > DHTGPU_MAX_K) {
+            for (size_t i = 0; i < q; ++i) res[i] = detail::cached_nodes_host(map, targets[i], count);
+            return res;
+        }
+        flush();
+        std::vector<uint8_t> t;
+        t.reserve(q * DHTGPU_HASH_LEN);
+        for (size_t i = 0; i < q; ++i) detail::put_id(t, targets[i]);
+        std::vector<uint32_t> h(q * count), cnt(q);
+        check(dhtgpu_nc_nodes(ctx_.get(), t.data(), (uint32_t)q, (uint32_t)count, h.data(), cnt.data()), "nc_nodes");
+        for (size_t i = 0; i < q; ++i) {
+            res[i].reserve(cnt[i]);
+            for (uint32_t r = 0; r < cnt[i]; ++r)
+                if (NodePtr n = s_.slots_[h[i * count + r]].lock()) res[i].push_back(n);
+        }
+        return res;
+    }
+
+    const Slots& slots() const { return s_; }
+
+private:
+    /* the mirror from the keys held: every key with its slot, then every slot's accept bit */
+    void rebuild() {
+        std::vector<uint8_t> ids;
+        std::vector<uint32_t> handles;
+        ids.reserve(s_.size() * DHTGPU_HASH_LEN);
+        handles.reserve(s_.size());
+        for (const auto& kh : s_.slot_of_) {
+            ids.insert(ids.end(), kh.first.b, kh.first.b + DHTGPU_HASH_LEN);
+            handles.push_back(kh.second);
+        }
+        check(dhtgpu_nc_set(ctx_.get(), ids.empty() ? nullptr : ids.data(), handles.empty() ? nullptr : handles.data(),
+                            s_.size()),
+              "nc_set");
+        refresh();
+    }
+    Context& ctx_;
+    Slots s_;
 };
 
 /* Drop-in for NetworkEngine::bufferNodes(af, id, nodes) (src/network_engine.cpp:1003-1032)

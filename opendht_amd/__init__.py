@@ -14,6 +14,8 @@ Reference interfaces mirrored (OpenDHT tree paths):
   Context.classify        RoutingTable::findBucket + InfoHash::commonBits
   Context.rt_set / rt_reply / rt_closer  the routing table resident on the device: onFindNode / onGetValues'
                           findClosestNodes + bufferNodes fused; maintainStorage / onAnnounce closeness tests
+  Context.nc_set / nc_insert / nc_erase / nc_nodes  NodeCache's map resident on the device, changed
+                          incrementally; getCachedNodes one wave per target (src/node_cache.cpp:42-123)
 """
 import ctypes
 import os
@@ -150,6 +152,16 @@ def lib():
                                   _vp, _vp], ctypes.c_int),
         "dhtgpu_rt_closer": ([_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u32p],
                              ctypes.c_int),
+        "dhtgpu_nc_set": ([_vp, _u8p, _u32p, ctypes.c_uint64], ctypes.c_int),
+        "dhtgpu_nc_insert": ([_vp, _u8p, _u32p, _u8p, ctypes.c_uint32, _u8p], ctypes.c_int),
+        "dhtgpu_nc_erase": ([_vp, _u8p, ctypes.c_uint32, _u8p], ctypes.c_int),
+        "dhtgpu_nc_update_accept": ([_vp, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_nc_set_accept": ([_vp, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_nc_size": ([_vp, _u64p], ctypes.c_int),
+        "dhtgpu_nc_export": ([_vp, _u8p, _u32p], ctypes.c_int),
+        "dhtgpu_nc_nodes_dev": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp],
+                                ctypes.c_int),
+        "dhtgpu_nc_nodes": ([_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("DHTGPU_LIB") and not hasattr(L, name):
@@ -179,7 +191,8 @@ def exported_symbols():
             "dhtgpu_update_accept", "dhtgpu_num_accepted", "dhtgpu_write_ids", "dhtgpu_batch_plan",
             "dhtgpu_rt_set", "dhtgpu_rt_set_good", "dhtgpu_rt_update_good", "dhtgpu_rt_find_closest_dev",
             "dhtgpu_rt_find_closest", "dhtgpu_rt_reply_dev", "dhtgpu_rt_reply", "dhtgpu_rt_closer_dev",
-            "dhtgpu_rt_closer"]
+            "dhtgpu_rt_closer", "dhtgpu_nc_set", "dhtgpu_nc_insert", "dhtgpu_nc_erase", "dhtgpu_nc_update_accept",
+            "dhtgpu_nc_set_accept", "dhtgpu_nc_size", "dhtgpu_nc_export", "dhtgpu_nc_nodes_dev", "dhtgpu_nc_nodes"]
 
 
 def _ids(a, name="ids"):
@@ -488,6 +501,80 @@ class Context:
     def rt_closer_dev(self, t_planes_ptr, t_stride, q, count, min_nodes, out_flag_ptr, out_cnt_ptr=None, stream=None):
         _check(lib().dhtgpu_rt_closer_dev(self._h, t_planes_ptr, t_stride, q, count, min_nodes, out_flag_ptr,
                                           out_cnt_ptr, stream), "rt_closer_dev")
+
+    # ---- K8w: the resident NodeCache ------------------------------------------------
+    def nc_set(self, ids, handles=None):
+        """Replace the mirror with (n, 20) keys in any order; handles (n,) uint32 (None: key i has
+        handle i).  Every handle starts accepted."""
+        ids = _ids(ids) if len(ids) else np.zeros((0, 20), np.uint8)
+        h = None
+        if handles is not None:
+            h = np.ascontiguousarray(handles, dtype=np.uint32).reshape(-1)
+            if h.shape[0] != ids.shape[0]:
+                raise ValueError("handles must have one entry per key")
+        _check(lib().dhtgpu_nc_set(self._h, _p(ids, _u8p), _p(h, _u32p) if h is not None else None, ids.shape[0]),
+               "nc_set")
+
+    def nc_insert(self, ids, handles, accept=None):
+        """std::map::emplace for m keys: (m,) uint8, 1 where the key was inserted (else it was
+        present, or an earlier key of the batch equals it).  accept (m,) sets the new keys' bits."""
+        ids = _ids(ids) if len(ids) else np.zeros((0, 20), np.uint8)
+        h = np.ascontiguousarray(handles, dtype=np.uint32).reshape(-1)
+        if h.shape[0] != ids.shape[0]:
+            raise ValueError("handles must have one entry per key")
+        a = None
+        if accept is not None:
+            a = np.ascontiguousarray(np.asarray(accept).reshape(-1) != 0, dtype=np.uint8)
+            if a.shape[0] != ids.shape[0]:
+                raise ValueError("accept must have one entry per key")
+        new = np.zeros(ids.shape[0], dtype=np.uint8)
+        _check(lib().dhtgpu_nc_insert(self._h, _p(ids, _u8p), _p(h, _u32p), _p(a, _u8p) if a is not None else None,
+                                      ids.shape[0], _p(new, _u8p)), "nc_insert")
+        return new
+
+    def nc_erase(self, ids):
+        """map.erase(key) for m keys: (m,) uint8, 1 where the key was erased."""
+        ids = _ids(ids) if len(ids) else np.zeros((0, 20), np.uint8)
+        found = np.zeros(ids.shape[0], dtype=np.uint8)
+        _check(lib().dhtgpu_nc_erase(self._h, _p(ids, _u8p), ids.shape[0], _p(found, _u8p)), "nc_erase")
+        return found
+
+    def nc_update_accept(self, handles, val):
+        """accept bit of handles[j] = val[j] (val: array or one value for all); stream-ordered."""
+        h = np.ascontiguousarray(handles, dtype=np.uint32).reshape(-1)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(val), h.shape)).astype(np.uint8).reshape(-1)
+        _check(lib().dhtgpu_nc_update_accept(self._h, _p(h, _u32p), _p(v, _u8p), h.shape[0]), "nc_update_accept")
+
+    def nc_set_accept(self, accept_by_handle):
+        """accept bit of handle h = accept_by_handle[h] for h < len; stream-ordered."""
+        a = np.ascontiguousarray(np.asarray(accept_by_handle).reshape(-1) != 0, dtype=np.uint8)
+        _check(lib().dhtgpu_nc_set_accept(self._h, _p(a, _u8p) if a.size else None, a.shape[0]), "nc_set_accept")
+
+    def nc_size(self):
+        n = ctypes.c_uint64(0)
+        _check(lib().dhtgpu_nc_size(self._h, ctypes.byref(n)), "nc_size")
+        return int(n.value)
+
+    def nc_export(self):
+        """The mirror in lexicographic order: (n, 20) keys, (n,) handles."""
+        n = self.nc_size()
+        ids = np.zeros((n, 20), dtype=np.uint8)
+        h = np.zeros(n, dtype=np.uint32)
+        _check(lib().dhtgpu_nc_export(self._h, _p(ids, _u8p), _p(h, _u32p)), "nc_export")
+        return ids, h
+
+    def nc_nodes(self, targets, count=8):
+        """getCachedNodes over the mirror: (q, count) handles in walk order (NONE padded), (q,) counts."""
+        t = _ids(targets, "targets") if len(targets) else np.zeros((0, 20), np.uint8)
+        q = t.shape[0]
+        out = np.empty((q, count), dtype=np.uint32)
+        cnt = np.empty(q, dtype=np.uint32)
+        _check(lib().dhtgpu_nc_nodes(self._h, _p(t, _u8p), q, count, _p(out, _u32p), _p(cnt, _u32p)), "nc_nodes")
+        return out, cnt
+
+    def nc_nodes_dev(self, t_planes_ptr, t_stride, q, count, out_handle_ptr, out_cnt_ptr, stream=None):
+        _check(lib().dhtgpu_nc_nodes_dev(self._h, t_planes_ptr, t_stride, q, count, out_handle_ptr, out_cnt_ptr,
+                                         stream), "nc_nodes_dev")
 
     # ---- a11 / f4: compact node wire format ---------------------------------------
     def buffer_nodes(self, node_tail, af, targets, cand):

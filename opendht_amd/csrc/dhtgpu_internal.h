@@ -260,6 +260,41 @@ hipError_t launch_rt_reply(const RtView& v, const uint32_t* tp, uint64_t ts, uin
 hipError_t launch_rt_closer(const RtView& v, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t count,
                             uint32_t min_nodes, uint8_t* out_flag, uint32_t* out_cnt, hipStream_t s);
 
+// ncache.hip: K8w, the resident NodeCache mirror (dhtgpu_nc_*).  The mirror as the kernels read
+// it: device pointers into the context's current buffer set and its accept mask.
+struct NcView {
+    uint32_t n;              // keys
+    const uint32_t* kp;      // key word planes, lexicographically sorted: kp[w * ks + i]
+    uint64_t ks;
+    const uint32_t* hp;      // [n] the caller's handle of key i (= kp + 5 * ks)
+    const uint32_t* bits;    // accept mask by handle: bit (h & 31) of word h >> 5; covers every handle of hp
+};
+// getCachedNodes per target over the mirror (1 <= count <= DHTGPU_MAX_K_DEV): handles in walk order + counts
+hipError_t launch_nc_nodes(const NcView& v, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t count,
+                           uint32_t* out_handle, uint32_t* out_cnt, hipStream_t s);
+// A sorted batch (bp / bs, perm[j] = caller index of sorted key j, m keys) against the mirror:
+// rank[j] = its lower bound, flag[j] = the mutation applies to it (insert: not resident; erase:
+// resident; never to a repeat of the batch key before it), res[perm[j]] = flag[j], bsum / boff
+// [ceil(m / 256)] = the set flags per 256-key block and their exclusive scan, *d_total = their
+// sum, kpos / ksrc [e] = rank[j] / j of the e-th kept key.
+hipError_t launch_nc_rank(bool erase, const NcView& v, const uint32_t* bp, uint64_t bs, const uint32_t* perm, uint32_t m,
+                          uint32_t* rank, uint32_t* flag, uint32_t* bsum, uint32_t* boff, uint32_t* kpos, uint32_t* ksrc,
+                          uint32_t* d_total, uint8_t* res, hipStream_t s);
+// The one pass of a mutation: the mirror and the cnt kept batch keys (handles hin[], accept bytes
+// ain[] -- nullable: accepted -- in the caller's order; their accept bits are set in `bits`) into
+// the six planes at dst (stride ds >= n + cnt) / the mirror without the cnt positions kpos[].
+hipError_t launch_nc_insert(const NcView& v, uint32_t* dst, uint64_t ds, const uint32_t* kpos, const uint32_t* ksrc,
+                            uint32_t cnt, const uint32_t* bp, uint64_t bs, const uint32_t* perm, const uint32_t* hin,
+                            const uint8_t* ain, uint32_t* bits, hipStream_t s);
+hipError_t launch_nc_erase(const NcView& v, uint32_t* dst, uint64_t ds, const uint32_t* kpos, uint32_t cnt,
+                           hipStream_t s);
+// hp[j] = hin[perm[j]] with its accept bit set, or perm[j] when hin is null (bits untouched)
+hipError_t launch_nc_handles(const uint32_t* perm, const uint32_t* hin, uint32_t n, uint32_t* hp, uint32_t* bits,
+                             hipStream_t s);
+// bit handles[j] = val[j] != 0, j < m; bits [0, nh) from bytes[nh] (device arrays, handles in range)
+hipError_t launch_nc_bits_set(uint32_t* bits, const uint32_t* handles, const uint8_t* val, uint32_t m, hipStream_t s);
+hipError_t launch_nc_bits_pack(const uint8_t* bytes, uint32_t nh, uint32_t* bits, hipStream_t s);
+
 // crawl.hip: crawl-replay model (iterative searches over implicit routing tables)
 uint32_t search_list_cap();
 // sorts the K4 index buckets (index workspace, n ids, B bits) by (w0, index) into out[n]
