@@ -35,6 +35,10 @@
  *   dhtgpu_nc_set/_insert/_erase  NodeCache's map (node_cache.h:43) resident on the device, changed
  *                          incrementally (NodeMap::getNode, clearBadNodes: src/node_cache.cpp:87-123)
  *   dhtgpu_nc_nodes        NodeCache::getCachedNodes (src/node_cache.cpp:42-74) over it, one wave per target
+ *   dhtgpu_sr_insert       Search::insertNode (src/search.h:636-722) over node lists resident on the device,
+ *                          one wave per search
+ *   dhtgpu_sr_refill       Dht::refill (src/dht.cpp:656-677): getCachedNodes over the nc mirror + insertNode, fused
+ *   dhtgpu_sr_status       Search::getNumberOfBadNodes / getNumberOfConsecutiveBadNodes (src/search.h:516-530)
  *
  * Threading (mirrors the reference, src/dhtrunner.cpp:115-150): one context per
  * thread, or external locking; every host-pointer call is synchronous.
@@ -420,6 +424,82 @@ int dhtgpu_nc_nodes_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_st
                         uint32_t* out_handle, uint32_t* out_cnt, void* stream);
 int dhtgpu_nc_nodes(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, uint32_t count, uint32_t* out_handle,
                     uint32_t* out_cnt);
+
+/* ---- K10w: the resident searches --------------------------------------------------------------- */
+/* The node lists of a node's searches (Dht::Search::nodes, src/search.h; up to MAX_SEARCHES = 16384)
+ * kept on the device between calls, so that Search::insertNode (src/search.h:636-722) and a batch
+ * of Dht::refill (src/dht.cpp:656-677) run with no list, node table or cache result crossing PCIe.
+ * One search set per context, private to the sr entry points.  A search lives in a SLOT in
+ * [0, nslots).  A list entry is {handle, 160-bit id, flags}: flags are bit0 candidate and bit1
+ * replied, as in dhtgpu_search_insert, and the node's identity is its HANDLE -- the handle space of
+ * dhtgpu_nc_*, below DHTGPU_NC_MAX_HANDLE; one handle per id is the caller's business, as it is
+ * there.  A row holds DHTGPU_SR_CAP entries; host arrays of rows use that stride and DHTGPU_NONE
+ * padding.  Every sr call but dhtgpu_sr_reset returns DHTGPU_ENOIDS before the first reset; a slot
+ * >= nslots or a handle >= DHTGPU_NC_MAX_HANDLE in a host array is DHTGPU_EINVAL before any launch
+ * (the _dev forms skip such a slot).
+ *
+ * Ordering: every sr call is ordered on the context's stream (the _dev forms on the stream they
+ * are given); insert, refill, status and lists are stream-ordered against each other.  The host
+ * forms that return data synchronise; reset, open, expire, set_candidate and the state setters do
+ * not.  dhtgpu_nc_insert and dhtgpu_nc_erase stay synchronous and must not be issued while a
+ * dhtgpu_sr_refill_dev is in flight on another stream.
+ *
+ * dhtgpu_sr_reset creates nslots empty searches (nslots <= 2^20, else DHTGPU_ERANGE) and drops any
+ * earlier set and the state array.  dhtgpu_sr_open: a new Search in each listed slot -- target
+ * set, list empty, expired = 0, overflow bit cleared.  dhtgpu_sr_expire: Search::expire()
+ * (src/search.h:560-565), expired = 1 and the list cleared. */
+#define DHTGPU_SR_CAP 64u
+int dhtgpu_sr_reset(dhtgpu_ctx* ctx, uint32_t nslots);
+int dhtgpu_sr_open(dhtgpu_ctx* ctx, const uint32_t* slots, const uint8_t* targets20, uint32_t m);
+int dhtgpu_sr_expire(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m);
+/* Node state, one byte per handle: bit0 Node::isExpired(), bit1 Node::isRemovable(now) -- the
+ * node_state of dhtgpu_search_insert, resident.  set replaces the array and its extent nh; update
+ * writes m handles (distinct) and grows the array, new bytes 0.  A kernel reads a handle at or past
+ * the extent as state 0 (the load is guarded).  Both run on the context's stream without
+ * synchronising, like dhtgpu_nc_set_accept / dhtgpu_nc_update_accept. */
+int dhtgpu_sr_set_state(dhtgpu_ctx* ctx, const uint8_t* state_by_handle, uint32_t nh);
+int dhtgpu_sr_update_state(dhtgpu_ctx* ctx, const uint32_t* handles, const uint8_t* val, uint32_t m);
+/* Dht::searchNodeGetExpired's srn->candidate = not over (src/dht.cpp:249-250) for m distinct
+ * (slot, handle) pairs: the entry's candidate flag = val[j] != 0; a handle that is not in the
+ * slot's list changes nothing. */
+int dhtgpu_sr_set_candidate(dhtgpu_ctx* ctx, const uint32_t* slots, const uint32_t* handles, const uint8_t* val,
+                            uint32_t m);
+/* Search::insertNode (src/search.h:636-722) + removeExpiredNode (:541-551), one wave per search:
+ * slot slots[j] takes insertions [ins_off[j], ins_off[j+1]) in order -- handle, id, token byte
+ * (ins_token nullable: no tokens) -- and ins_added (nullable) gets insertNode's return values.  The
+ * semantics are dhtgpu_search_insert's (trimming that pops the node which just carried a token
+ * included), except that "the same node" means "the same handle".  The slots of one call are
+ * distinct (host form: DHTGPU_EINVAL otherwise).  An insertion that would make a list longer than
+ * DHTGPU_SR_CAP is dropped: the slot's overflow bit is set (until the slot is opened again), the
+ * row stays a valid list and the slot's next insertions are applied; the host forms of insert and
+ * refill then return DHTGPU_ERANGE after applying everything else, the _dev forms report it through
+ * the status bit only.  _dev: every array on the device (ids as word planes, id_stride >= the number
+ * of insertions), a stream (NULL = the context's); it neither synchronises nor allocates. */
+int dhtgpu_sr_insert(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, const uint64_t* ins_off,
+                     const uint32_t* ins_handle, const uint8_t* ins_ids20, const uint8_t* ins_token,
+                     uint8_t* ins_added);
+int dhtgpu_sr_insert_dev(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, const uint64_t* ins_off,
+                         const uint32_t* ins_handle, const uint32_t* id_planes, uint64_t id_stride,
+                         const uint8_t* ins_token, uint8_t* ins_added, void* stream);
+/* Dht::refill (src/dht.cpp:656-677) for m searches in one launch: getCachedNodes(the slot's
+ * target, count) over this context's nc mirror and its current accept bits -- the walk and the
+ * walk order of dhtgpu_nc_nodes -- then insertNode(node, no token) for each result in that order;
+ * out_inserted[j] = refill's return value.  1 <= count <= DHTGPU_MAX_K (the reference passes
+ * SEARCH_NODES = 14); DHTGPU_ENOIDS without an nc mirror. */
+int dhtgpu_sr_refill(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t count, uint32_t* out_inserted);
+int dhtgpu_sr_refill_dev(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t count, uint32_t* out_inserted,
+                         void* stream);
+/* out4[j*4 ..] = {len, getNumberOfBadNodes, getNumberOfConsecutiveBadNodes (src/search.h:516-530,
+ * isBad = expired state || candidate), bits: bit0 expired, bit1 overflowed} -- what searchStep's
+ * expiry test (src/dht.cpp:641-642) reads. */
+int dhtgpu_sr_status(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t* out4);
+int dhtgpu_sr_status_dev(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t* out4, void* stream);
+/* The rows, closest first (Search::getNodes order): out_handle[m * DHTGPU_SR_CAP], out_flags
+ * (nullable, same shape), out_len[m] (nullable). */
+int dhtgpu_sr_lists(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
+                    uint32_t* out_len);
+int dhtgpu_sr_lists_dev(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
+                        uint32_t* out_len, void* stream);
 
 /* ---- K2: routing-bucket classification over the context's id set -------------- */
 /* out_bucket[n] (nullable) = findBucket(id) index; hist161[161] = histogram of

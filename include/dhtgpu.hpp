@@ -742,6 +742,7 @@ public:
     }
 
     const Slots& slots() const { return s_; }
+    Context& context() const { return ctx_; }
 
 private:
     /* the mirror from the keys held: every key with its slot, then every slot's accept bit */
@@ -761,6 +762,235 @@ private:
     }
     Context& ctx_;
     Slots s_;
+};
+
+/* The searches' node lists resident on the device (dhtgpu_sr_*), on top of a ResidentCache: the
+ * same context, and a node's handle is its cache slot (every Node of the reference comes out of the
+ * NodeCache; what is queued for a node the cache no longer holds at the flush is skipped).  SearchT is the reference's
+ * Dht::Search shape: id, expired, nodes (a std::vector of SearchNode{node, candidate, ...},
+ * constructible from a shared_ptr<Node>) and insertNode(node, now).  Wiring:
+ *   open(id) -> slot            where Dht::search creates a Search; close(slot) where it is dropped
+ *                               (closed slots go on a free list, like the cache's)
+ *   noteInsert(slot, node, has_token)   where the reply path calls sr->insertNode(node, now, token)
+ *   noteCandidate(slot, node, val)      where Dht::searchNodeGetExpired sets srn->candidate
+ *                               -- all three only queue: no device call before the next flush
+ *   refresh(now)                once per sweep: flushes the queue, then isExpired() | isRemovable(now) << 1
+ *                               of every live cache slot, as one upload
+ *   refillBatch(searches, slots, q, now)   Dht::refill for q searches; returns the inserted counts
+ * Below min_device_batch searches refillBatch runs the reference's body on the host
+ * (detail::cached_nodes_host on the map, then sr.insertNode) and queues what it inserted: no device
+ * call, so one refill costs what the reference's costs.  From the threshold up it flushes the
+ * cache's queue and its own, runs dhtgpu_sr_refill, reads the rows back and reconciles each host
+ * Search: nodes becomes the device row in its order, keeping the SearchNode of a node that was
+ * listed and making a new one (node->setTime(now)) for a new node; expired is copied.  The device
+ * applies queued insertions with the node state of the last refresh.  dhtgpu::Error on a device
+ * failure: the caller falls back to the host body as INTEGRATION.md shows. */
+/* Smallest batch refilled on the device, from the crossover measured in DESIGN.md §5l
+ * (profiles/r12/rsearch/rsearch_check_run.txt: refresh + refillBatch through this adapter against
+ * the host body, 6,000 keys, count 14, lists already full): the host body wins at 256 searches
+ * (176.7 against 195.7 us), the device at 512 (205.8 against 369.0 us); the two differences cross at
+ * 283 searches.  The constant is the next multiple of 64 at or above 1.1 x the crossover (311.3):
+ * the margin keeps box-to-box spread from putting the default on the losing side. */
+static const size_t kMinResidentRefillBatch = 320;
+
+template <class NodeMap, class SearchT, class Cache = ResidentCache<NodeMap>>
+class ResidentSearches {
+public:
+    typedef typename Cache::NodePtr NodePtr;
+    typedef typename Cache::Key Key;
+    typedef typename std::remove_reference<decltype(std::declval<SearchT&>().nodes[0])>::type SearchNodeT;
+    /* map: the NodeCache map the host body walks (it outlives this object) */
+    ResidentSearches(Cache& cache, const NodeMap& map, uint32_t nslots = 16384)
+        : min_device_batch(kMinResidentRefillBatch), cache_(cache), map_(map), nslots_(nslots), next_(0), ready_(false) {}
+    size_t min_device_batch;   // smallest batch refilled on the device
+
+    template <class HashT>
+    uint32_t open(const HashT& id) {
+        uint32_t s;
+        if (!free_.empty()) {
+            s = free_.back();
+            free_.pop_back();
+        } else {
+            if (next_ >= nslots_) throw Error(DHTGPU_ERANGE, "ResidentSearches: out of slots");
+            s = next_++;
+        }
+        Op op = {kOpen, s, 0, Cache::Slots::key_of(id), NodePtr()};
+        log_.push_back(op);
+        return s;
+    }
+    /* the slot goes to the free list; what was queued for it leaves the queue */
+    void close(uint32_t slot) {
+        size_t w = 0;
+        for (size_t i = 0; i < log_.size(); ++i)
+            if (log_[i].slot != slot) log_[w++] = log_[i];
+        log_.resize(w);
+        free_.push_back(slot);
+    }
+    void noteInsert(uint32_t slot, const NodePtr& node, bool has_token) {
+        Op op = {kInsert, slot, (uint8_t)(has_token ? 1 : 0), Key(), node};
+        log_.push_back(op);
+    }
+    void noteCandidate(uint32_t slot, const NodePtr& node, bool val) {
+        Op op = {kCandidate, slot, (uint8_t)(val ? 1 : 0), Key(), node};
+        log_.push_back(op);
+    }
+    size_t pending() const { return log_.size(); }
+    size_t freeSlots() const { return free_.size(); }
+
+    /* the queue in order, every run of one kind as one call */
+    void flush() {
+        ensure();
+        size_t i = 0;
+        while (i < log_.size()) {
+            size_t e = i;
+            while (e < log_.size() && log_[e].kind == log_[i].kind) ++e;
+            if (log_[i].kind == kOpen) flush_open(i, e);
+            else if (log_[i].kind == kInsert) flush_insert(i, e);
+            else flush_candidate(i, e);
+            i = e;
+        }
+        log_.clear();
+    }
+
+    template <class TimePoint>
+    void refresh(TimePoint now) {
+        flush();   // what is queued was done under the state the device still holds
+        const auto& sl = cache_.slots().slots_;
+        if (sl.empty()) return;
+        std::vector<uint8_t> st(sl.size());
+        for (size_t h = 0; h < st.size(); ++h)
+            if (const NodePtr n = sl[h].lock()) st[h] = (uint8_t)((n->isExpired() ? 1 : 0) | (n->isRemovable(now) ? 2 : 0));
+        check(dhtgpu_sr_set_state(ctx(), st.data(), (uint32_t)st.size()), "sr_set_state");
+    }
+
+    template <class TimePoint>
+    std::vector<unsigned> refillBatch(SearchT* const* searches, const uint32_t* slots, size_t q, TimePoint now,
+                                      size_t count = 14) {
+        std::vector<unsigned> inserted(q, 0);
+        if (q == 0) return inserted;
+        if (q < min_device_batch || count > DHTGPU_MAX_K) {   // Dht::refill's body
+            for (size_t i = 0; i < q; ++i) {
+                for (const NodePtr& n : detail::cached_nodes_host(map_, searches[i]->id, count)) {
+                    if (searches[i]->insertNode(n, now)) ++inserted[i];
+                    noteInsert(slots[i], n, false);
+                }
+            }
+            return inserted;
+        }
+        cache_.flush();
+        flush();
+        std::vector<uint32_t> ins(q), rows(q * DHTGPU_SR_CAP), lens(q), st(q * 4);
+        const int rc = dhtgpu_sr_refill(ctx(), slots, (uint32_t)q, (uint32_t)count, ins.data());
+        if (rc != DHTGPU_ERANGE) check(rc, "sr_refill");   // an overflowed row is still a valid list
+        check(dhtgpu_sr_lists(ctx(), slots, (uint32_t)q, rows.data(), nullptr, lens.data()), "sr_lists");
+        check(dhtgpu_sr_status(ctx(), slots, (uint32_t)q, st.data()), "sr_status");
+        const auto& sl = cache_.slots().slots_;
+        for (size_t i = 0; i < q; ++i) {
+            SearchT& sr = *searches[i];
+            const uint32_t* row = &rows[i * DHTGPU_SR_CAP];
+            // a slot names a listed node when both share their owner: no lock(), no key lookup
+            const auto listed = [&](uint32_t h, size_t j) {
+                const NodePtr& p = sr.nodes[j].node;
+                return p && h < sl.size() && !sl[h].owner_before(p) && !p.owner_before(sl[h]);
+            };
+            bool same = lens[i] == sr.nodes.size();   // the usual outcome: the row is the host list
+            for (uint32_t r = 0; same && r < lens[i]; ++r) same = listed(row[r], r);
+            if (!same) {
+                std::vector<SearchNodeT> nodes;
+                nodes.reserve(lens[i]);
+                size_t cur = 0;   // both lists are in distance order: a kept node is found from here on
+                for (uint32_t r = 0; r < lens[i]; ++r) {
+                    const size_t hn = sr.nodes.size();
+                    size_t k = cur;
+                    while (k < hn && !listed(row[r], k)) ++k;
+                    if (k == hn)
+                        for (k = 0; k < cur && !listed(row[r], k); ++k) {}
+                    if (k < hn && listed(row[r], k)) {
+                        nodes.push_back(std::move(sr.nodes[k]));
+                        sr.nodes[k].node.reset();
+                        if (k >= cur) cur = k + 1;
+                    } else if (NodePtr n = row[r] < sl.size() ? sl[row[r]].lock() : NodePtr()) {
+                        nodes.push_back(SearchNodeT(n));
+                        n->setTime(now);
+                    }
+                }
+                sr.nodes = std::move(nodes);
+            }
+            sr.expired = (st[i * 4 + 3] & 1u) != 0;
+            inserted[i] = ins[i];
+        }
+        return inserted;
+    }
+
+private:
+    enum Kind { kOpen, kInsert, kCandidate };
+    struct Op {
+        Kind kind;
+        uint32_t slot;
+        uint8_t val;    // insert: replied with a token; candidate: the flag
+        Key key;        // open: the target
+        NodePtr node;   // insert, candidate: the node (its cache slot is looked up when the queue is flushed,
+    };                  //   so queueing costs no key lookup; a node the cache dropped meanwhile is skipped)
+    dhtgpu_ctx* ctx() const { return cache_.context().get(); }
+    void ensure() {
+        if (ready_) return;
+        check(dhtgpu_sr_reset(ctx(), nslots_), "sr_reset");
+        ready_ = true;
+    }
+    void flush_open(size_t b, size_t e) {
+        std::vector<uint32_t> slots;
+        std::vector<uint8_t> t;
+        for (size_t i = b; i < e; ++i) {
+            slots.push_back(log_[i].slot);
+            t.insert(t.end(), log_[i].key.b, log_[i].key.b + DHTGPU_HASH_LEN);
+        }
+        check(dhtgpu_sr_open(ctx(), slots.data(), t.data(), (uint32_t)slots.size()), "sr_open");
+    }
+    void flush_insert(size_t b, size_t e) {   // grouped by slot, a slot's insertions in their order
+        std::map<uint32_t, std::vector<size_t>> by;
+        for (size_t i = b; i < e; ++i) by[log_[i].slot].push_back(i);
+        std::vector<uint32_t> slots, handles;
+        std::vector<uint64_t> off(1, 0);
+        std::vector<uint8_t> ids, tok;
+        for (const auto& kv : by) {
+            slots.push_back(kv.first);
+            for (size_t i : kv.second) {
+                const uint32_t h = cache_.slots().slotOf(log_[i].node->id);
+                if (h == DHTGPU_NONE) continue;
+                handles.push_back(h);
+                detail::put_id(ids, log_[i].node->id);
+                tok.push_back(log_[i].val);
+            }
+            off.push_back(handles.size());
+        }
+        if (handles.empty()) return;
+        const int rc = dhtgpu_sr_insert(ctx(), slots.data(), (uint32_t)slots.size(), off.data(), handles.data(), ids.data(),
+                                        tok.data(), nullptr);
+        if (rc != DHTGPU_ERANGE) check(rc, "sr_insert");
+    }
+    void flush_candidate(size_t b, size_t e) {   // of equal (slot, handle) pairs the last one counts
+        std::map<std::pair<uint32_t, uint32_t>, uint8_t> last;
+        for (size_t i = b; i < e; ++i) {
+            const uint32_t h = cache_.slots().slotOf(log_[i].node->id);
+            if (h != DHTGPU_NONE) last[std::make_pair(log_[i].slot, h)] = log_[i].val;
+        }
+        if (last.empty()) return;
+        std::vector<uint32_t> slots, handles;
+        std::vector<uint8_t> val;
+        for (const auto& kv : last) {
+            slots.push_back(kv.first.first);
+            handles.push_back(kv.first.second);
+            val.push_back(kv.second);
+        }
+        check(dhtgpu_sr_set_candidate(ctx(), slots.data(), handles.data(), val.data(), (uint32_t)slots.size()),
+              "sr_set_candidate");
+    }
+    Cache& cache_;
+    const NodeMap& map_;
+    uint32_t nslots_, next_;
+    bool ready_;
+    std::vector<uint32_t> free_;
+    std::vector<Op> log_;
 };
 
 /* Drop-in for NetworkEngine::bufferNodes(af, id, nodes) (src/network_engine.cpp:1003-1032)

@@ -16,6 +16,9 @@ Reference interfaces mirrored (OpenDHT tree paths):
                           findClosestNodes + bufferNodes fused; maintainStorage / onAnnounce closeness tests
   Context.nc_set / nc_insert / nc_erase / nc_nodes  NodeCache's map resident on the device, changed
                           incrementally; getCachedNodes one wave per target (src/node_cache.cpp:42-123)
+  Context.sr_reset / sr_open / sr_insert / sr_refill / sr_status / sr_lists  the searches' node lists
+                          resident on the device: Search::insertNode one wave per search
+                          (src/search.h:636-722), Dht::refill fused with getCachedNodes (src/dht.cpp:656-677)
 """
 import ctypes
 import os
@@ -28,6 +31,7 @@ __all__ = ["Context", "DhtGpuError", "NONE", "MAX_K", "lib", "LIB_PATH", "id_wor
 LIB_PATH = os.environ.get("DHTGPU_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdhtgpu.so")
 NONE = 0xFFFFFFFF
 MAX_K = 32
+SR_CAP = 64   # DHTGPU_SR_CAP: entries per resident search row
 # status codes (include/dhtgpu.h)
 EINVAL, ENOMEM, EDEVICE, ENOIDS, EUNSORTED, ERANGE = -1, -2, -3, -4, -5, -6
 
@@ -162,6 +166,21 @@ def lib():
         "dhtgpu_nc_nodes_dev": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp],
                                 ctypes.c_int),
         "dhtgpu_nc_nodes": ([_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_sr_reset": ([_vp, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_sr_open": ([_vp, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_sr_expire": ([_vp, _u32p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_sr_set_state": ([_vp, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_sr_update_state": ([_vp, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_sr_set_candidate": ([_vp, _u32p, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_sr_insert": ([_vp, _u32p, ctypes.c_uint32, _u64p, _u32p, _u8p, _u8p, _u8p], ctypes.c_int),
+        "dhtgpu_sr_insert_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp],
+                                 ctypes.c_int),
+        "dhtgpu_sr_refill": ([_vp, _u32p, ctypes.c_uint32, ctypes.c_uint32, _u32p], ctypes.c_int),
+        "dhtgpu_sr_refill_dev": ([_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
+        "dhtgpu_sr_status": ([_vp, _u32p, ctypes.c_uint32, _u32p], ctypes.c_int),
+        "dhtgpu_sr_status_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
+        "dhtgpu_sr_lists": ([_vp, _u32p, ctypes.c_uint32, _u32p, _u8p, _u32p], ctypes.c_int),
+        "dhtgpu_sr_lists_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("DHTGPU_LIB") and not hasattr(L, name):
@@ -192,7 +211,11 @@ def exported_symbols():
             "dhtgpu_rt_set", "dhtgpu_rt_set_good", "dhtgpu_rt_update_good", "dhtgpu_rt_find_closest_dev",
             "dhtgpu_rt_find_closest", "dhtgpu_rt_reply_dev", "dhtgpu_rt_reply", "dhtgpu_rt_closer_dev",
             "dhtgpu_rt_closer", "dhtgpu_nc_set", "dhtgpu_nc_insert", "dhtgpu_nc_erase", "dhtgpu_nc_update_accept",
-            "dhtgpu_nc_set_accept", "dhtgpu_nc_size", "dhtgpu_nc_export", "dhtgpu_nc_nodes_dev", "dhtgpu_nc_nodes"]
+            "dhtgpu_nc_set_accept", "dhtgpu_nc_size", "dhtgpu_nc_export", "dhtgpu_nc_nodes_dev", "dhtgpu_nc_nodes",
+            "dhtgpu_sr_reset", "dhtgpu_sr_open", "dhtgpu_sr_expire", "dhtgpu_sr_set_state", "dhtgpu_sr_update_state",
+            "dhtgpu_sr_set_candidate", "dhtgpu_sr_insert", "dhtgpu_sr_insert_dev", "dhtgpu_sr_refill",
+            "dhtgpu_sr_refill_dev", "dhtgpu_sr_status", "dhtgpu_sr_status_dev", "dhtgpu_sr_lists",
+            "dhtgpu_sr_lists_dev"]
 
 
 def _ids(a, name="ids"):
@@ -575,6 +598,117 @@ class Context:
     def nc_nodes_dev(self, t_planes_ptr, t_stride, q, count, out_handle_ptr, out_cnt_ptr, stream=None):
         _check(lib().dhtgpu_nc_nodes_dev(self._h, t_planes_ptr, t_stride, q, count, out_handle_ptr, out_cnt_ptr,
                                          stream), "nc_nodes_dev")
+
+    # ---- K10w: the resident searches ------------------------------------------------
+    @staticmethod
+    def _u32(a):
+        return np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+
+    def sr_reset(self, nslots):
+        """nslots empty searches; drops any earlier set and the state array."""
+        _check(lib().dhtgpu_sr_reset(self._h, nslots), "sr_reset")
+
+    def sr_open(self, slots, targets):
+        """A new Search (target, empty list, not expired) in each listed slot; stream-ordered."""
+        s = self._u32(slots)
+        t = _ids(targets, "targets") if len(targets) else np.zeros((0, 20), np.uint8)
+        if t.shape[0] != s.shape[0]:
+            raise ValueError("targets must have one row per slot")
+        _check(lib().dhtgpu_sr_open(self._h, _p(s, _u32p), _p(t, _u8p), s.shape[0]), "sr_open")
+
+    def sr_expire(self, slots):
+        """Search::expire(): expired = 1 and the list cleared; stream-ordered."""
+        s = self._u32(slots)
+        _check(lib().dhtgpu_sr_expire(self._h, _p(s, _u32p), s.shape[0]), "sr_expire")
+
+    def sr_set_state(self, state_by_handle):
+        """node state byte (bit0 isExpired, bit1 isRemovable) of handle h = state_by_handle[h]; replaces the array."""
+        a = np.ascontiguousarray(state_by_handle, dtype=np.uint8).reshape(-1)
+        _check(lib().dhtgpu_sr_set_state(self._h, _p(a, _u8p) if a.size else None, a.shape[0]), "sr_set_state")
+
+    def sr_update_state(self, handles, val):
+        """state byte of handles[j] = val[j] (val: array or one value for all); grows the array."""
+        h = self._u32(handles)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(val), h.shape)).astype(np.uint8).reshape(-1)
+        _check(lib().dhtgpu_sr_update_state(self._h, _p(h, _u32p), _p(v, _u8p), h.shape[0]), "sr_update_state")
+
+    def sr_set_candidate(self, slots, handles, val):
+        """candidate flag of handles[j]'s entry in slots[j] = val[j]; an absent handle changes nothing."""
+        s, h = self._u32(slots), self._u32(handles)
+        if s.shape[0] != h.shape[0]:
+            raise ValueError("one handle per slot")
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(val), h.shape)).astype(np.uint8).reshape(-1)
+        _check(lib().dhtgpu_sr_set_candidate(self._h, _p(s, _u32p), _p(h, _u32p), _p(v, _u8p), s.shape[0]),
+               "sr_set_candidate")
+
+    def sr_insert(self, slots, ins_off, ins_handle, ins_ids, ins_token=None):
+        """Search::insertNode: slots[j] takes insertions [ins_off[j], ins_off[j+1]) in order.  Returns
+        the (total,) uint8 insertNode results; raises ERANGE (after applying everything else) when a
+        list overflowed -- the results are then in the exception's `added`."""
+        s = self._u32(slots)
+        off = np.ascontiguousarray(ins_off, dtype=np.uint64).reshape(-1)
+        if off.shape[0] != s.shape[0] + 1:
+            raise ValueError("ins_off must have len(slots) + 1 entries")
+        h = self._u32(ins_handle)
+        ids = _ids(ins_ids) if len(ins_ids) else np.zeros((0, 20), np.uint8)
+        tot = int(off[-1])
+        if h.shape[0] < tot or ids.shape[0] < tot:
+            raise ValueError("ins_handle / ins_ids shorter than ins_off[-1]")
+        tok = None if ins_token is None else np.ascontiguousarray(ins_token, dtype=np.uint8).reshape(-1)
+        if tok is not None and tok.shape[0] < tot:
+            raise ValueError("ins_token shorter than ins_off[-1]")
+        added = np.zeros(tot, dtype=np.uint8)
+        code = lib().dhtgpu_sr_insert(self._h, _p(s, _u32p), s.shape[0], _p(off, _u64p), _p(h, _u32p), _p(ids, _u8p),
+                                      _p(tok, _u8p) if tok is not None else None, _p(added, _u8p))
+        if code != 0:
+            e = DhtGpuError(code, "sr_insert")
+            e.added = added
+            raise e
+        return added
+
+    def sr_refill(self, slots, count=14):
+        """Dht::refill per slot over the nc mirror: (m,) uint32 inserted counts; ERANGE as sr_insert
+        (the counts in the exception's `inserted`)."""
+        s = self._u32(slots)
+        out = np.zeros(s.shape[0], dtype=np.uint32)
+        code = lib().dhtgpu_sr_refill(self._h, _p(s, _u32p), s.shape[0], count, _p(out, _u32p))
+        if code != 0:
+            e = DhtGpuError(code, "sr_refill")
+            e.inserted = out
+            raise e
+        return out
+
+    def sr_status(self, slots):
+        """(m, 4) uint32: len, bad nodes, leading bad nodes, bits (bit0 expired, bit1 overflowed)."""
+        s = self._u32(slots)
+        out = np.zeros((s.shape[0], 4), dtype=np.uint32)
+        _check(lib().dhtgpu_sr_status(self._h, _p(s, _u32p), s.shape[0], _p(out, _u32p)), "sr_status")
+        return out
+
+    def sr_lists(self, slots):
+        """The rows closest first: (m, 64) handles (NONE padded), (m, 64) flags, (m,) lengths."""
+        s = self._u32(slots)
+        m = s.shape[0]
+        h = np.full((m, SR_CAP), NONE, dtype=np.uint32)
+        fl = np.zeros((m, SR_CAP), dtype=np.uint8)
+        ln = np.zeros(m, dtype=np.uint32)
+        _check(lib().dhtgpu_sr_lists(self._h, _p(s, _u32p), m, _p(h, _u32p), _p(fl, _u8p), _p(ln, _u32p)), "sr_lists")
+        return h, fl, ln
+
+    def sr_insert_dev(self, slots_ptr, m, ins_off_ptr, ins_handle_ptr, id_planes_ptr, id_stride, ins_token_ptr,
+                      ins_added_ptr, stream=None):
+        _check(lib().dhtgpu_sr_insert_dev(self._h, slots_ptr, m, ins_off_ptr, ins_handle_ptr, id_planes_ptr, id_stride,
+                                          ins_token_ptr, ins_added_ptr, stream), "sr_insert_dev")
+
+    def sr_refill_dev(self, slots_ptr, m, count, out_inserted_ptr, stream=None):
+        _check(lib().dhtgpu_sr_refill_dev(self._h, slots_ptr, m, count, out_inserted_ptr, stream), "sr_refill_dev")
+
+    def sr_status_dev(self, slots_ptr, m, out4_ptr, stream=None):
+        _check(lib().dhtgpu_sr_status_dev(self._h, slots_ptr, m, out4_ptr, stream), "sr_status_dev")
+
+    def sr_lists_dev(self, slots_ptr, m, out_handle_ptr, out_flags_ptr=None, out_len_ptr=None, stream=None):
+        _check(lib().dhtgpu_sr_lists_dev(self._h, slots_ptr, m, out_handle_ptr, out_flags_ptr, out_len_ptr, stream),
+               "sr_lists_dev")
 
     # ---- a11 / f4: compact node wire format ---------------------------------------
     def buffer_nodes(self, node_tail, af, targets, cand):

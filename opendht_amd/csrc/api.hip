@@ -7,7 +7,7 @@
 // everything in order and an early return leaks nothing.
 // Layout: owners and the context; helpers shared by several entry points (each sequence stands
 // once); then the entry points by family -- id set, accept mask, K1, K4, K6, table, caches,
-// wire format, searches, the resident routing table, the resident NodeCache, crawl model.
+// wire format, searches, the resident routing table, the resident NodeCache, the resident searches, crawl model.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
@@ -274,6 +274,22 @@ struct dhtgpu_ctx {
             return NcView{n, p, cap[cur], p + 5 * cap[cur], bits.as<uint32_t>()};
         }
     } nc;
+    // Resident searches (dhtgpu_sr_reset ...): the rows' six entry planes, the slots' targets,
+    // lengths and bits bytes, and the node state bytes by handle (grown geometrically; the array
+    // before its last growth is kept for calls in flight on other streams).  Private to the sr
+    // entry points, staging included; refill reads the nc mirror through nc.view().
+    struct Searches {
+        DevBuf rows, tp, len, bits;
+        uint32_t nslots = 0;
+        DevBuf st, st_old;
+        uint32_t nst = 0;           // the state array's extent
+        DevBuf io;                  // host forms: argument and result staging
+        bool valid = false;
+        SrView view() const {
+            return SrView{nslots, rows.as<uint32_t>(), (uint64_t)nslots * DHTGPU_SR_CAP, tp.as<uint32_t>(),
+                          len.as<uint32_t>(), bits.as<uint8_t>(), st.as<uint8_t>(), nst};
+        }
+    } sr;
     // diagnostics: DHTGPU_DBG, the library's one diagnostics switch, read once at creation and
     // masked to kDbgAllowed -- bit 256: per-block phase stamps of F2 / F3 printed to stderr;
     // bit 2^23: K6 instead of KS for batches of <= 64 targets (both exact).  Neither changes a
@@ -2238,6 +2254,288 @@ int dhtgpu_nc_nodes(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t coun
                      [&](const uint32_t* tp, uint64_t ts, uint32_t* d_h, uint32_t* d_cnt) {
         return dhtgpu_nc_nodes_dev(c, tp, ts, q, count, d_h, d_cnt, c->stream);
     });
+}
+
+// ---- K10w: the resident searches ---------------------------------------------------------------
+}  // extern "C"
+
+// every slot names a search; `distinct`: no slot twice
+static int sr_check_slots(const dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, bool distinct) {
+    for (uint32_t j = 0; j < m; ++j)
+        if (slots[j] >= c->sr.nslots) return DHTGPU_EINVAL;
+    if (distinct && m > 1) {
+        std::vector<uint32_t> s(slots, slots + m);
+        std::sort(s.begin(), s.end());
+        if (std::adjacent_find(s.begin(), s.end()) != s.end()) return DHTGPU_EINVAL;
+    }
+    return DHTGPU_OK;
+}
+
+// The state array covers handles [0, nh), what it held kept and its new bytes 0: it grows
+// geometrically on the context's stream, and the array it replaces is kept until the next growth.
+static int sr_state_extent(dhtgpu_ctx* c, uint64_t nh) {
+    dhtgpu_ctx::Searches& t = c->sr;
+    if (nh <= t.nst) return DHTGPU_OK;
+    if (nh > t.st.cap) {
+        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(nh, std::max<uint64_t>(2 * t.st.cap, 4096)),
+                                                DHTGPU_NC_MAX_HANDLE);
+        DevBuf nb;
+        DHT_TRY(nb.ensure((size_t)cap));
+        if (t.nst) DHT_TRY(hipMemcpyAsync(nb.p, t.st.p, t.nst, hipMemcpyDeviceToDevice, c->stream));
+        t.st_old = std::move(t.st);   // (st_old's previous buffer goes with nb)
+        t.st = std::move(nb);
+    }
+    DHT_TRY(hipMemsetAsync(t.st.as<uint8_t>() + t.nst, 0, (size_t)(nh - t.nst), c->stream));
+    t.nst = (uint32_t)nh;
+    return DHTGPU_OK;
+}
+
+// m slots (host) into the head of the staging block p
+static int sr_upload_slots(dhtgpu_ctx* c, uint8_t* p, const uint32_t* slots, uint32_t m) {
+    DHT_TRY(hipMemcpyAsync(p, slots, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+    return DHTGPU_OK;
+}
+
+// the argument checks every sr call on a slot list shares
+static int sr_check(const dhtgpu_ctx* c, const void* slots, uint32_t m) {
+    if (!c || (m && !slots)) return DHTGPU_EINVAL;
+    if (!c->sr.valid) return DHTGPU_ENOIDS;
+    return DHTGPU_OK;
+}
+
+// the overflow word of a host insert / refill, read back after the call's other results
+static int sr_finish(dhtgpu_ctx* c, const uint32_t* d_over) {
+    uint32_t over = 0;
+    DHT_TRY(hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    return over ? DHTGPU_ERANGE : DHTGPU_OK;
+}
+
+extern "C" {
+
+int dhtgpu_sr_reset(dhtgpu_ctx* c, uint32_t nslots) {
+    if (!c) return DHTGPU_EINVAL;
+    if (nslots > (1u << 20)) return DHTGPU_ERANGE;
+    DHT_TRY(c->bind());
+    dhtgpu_ctx::Searches& t = c->sr;
+    t.valid = false;
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    t.st.release();
+    t.st_old.release();
+    t.nst = 0;
+    t.nslots = 0;
+    const size_t ns = nslots ? nslots : 1;
+    DHT_TRY(t.rows.ensure(ns * DHTGPU_SR_CAP * 6 * 4));
+    DHT_TRY(t.tp.ensure(ns * 5 * 4));
+    DHT_TRY(t.len.ensure(ns * 4));
+    DHT_TRY(t.bits.ensure(ns));
+    DHT_TRY(hipMemsetAsync(t.tp.p, 0, ns * 5 * 4, c->stream));
+    DHT_TRY(hipMemsetAsync(t.len.p, 0, ns * 4, c->stream));
+    DHT_TRY(hipMemsetAsync(t.bits.p, 0, ns, c->stream));
+    t.nslots = nslots;
+    t.valid = true;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_open(dhtgpu_ctx* c, const uint32_t* slots, const uint8_t* t20, uint32_t m) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && !t20) return DHTGPU_EINVAL;
+    if (int r = sr_check_slots(c, slots, m, false)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(c->sr.io.ensure((size_t)m * 4));
+    if (int r = sr_upload_slots(c, c->sr.io.as<uint8_t>(), slots, m)) return r;
+    uint64_t ts = 0;
+    DHT_TRY(c->upload_targets(t20, m, &ts));
+    DHT_TRY(launch_sr_open(c->sr.view(), c->sr.io.as<uint32_t>(), c->targets.as<uint32_t>(), ts, m, c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_expire(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (int r = sr_check_slots(c, slots, m, false)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(c->sr.io.ensure((size_t)m * 4));
+    if (int r = sr_upload_slots(c, c->sr.io.as<uint8_t>(), slots, m)) return r;
+    DHT_TRY(launch_sr_expire(c->sr.view(), c->sr.io.as<uint32_t>(), m, c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_set_state(dhtgpu_ctx* c, const uint8_t* state_by_handle, uint32_t nh) {
+    if (!c || (nh && !state_by_handle) || nh > DHTGPU_NC_MAX_HANDLE) return DHTGPU_EINVAL;
+    if (!c->sr.valid) return DHTGPU_ENOIDS;
+    DHT_TRY(c->bind());
+    c->sr.nst = 0;   // the array is replaced: nothing of it is kept
+    if (int r = sr_state_extent(c, nh)) return r;
+    if (nh) DHT_TRY(hipMemcpyAsync(c->sr.st.p, state_by_handle, nh, hipMemcpyHostToDevice, c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_update_state(dhtgpu_ctx* c, const uint32_t* handles, const uint8_t* val, uint32_t m) {
+    if (!c || (m && (!handles || !val))) return DHTGPU_EINVAL;
+    if (!c->sr.valid) return DHTGPU_ENOIDS;
+    const uint64_t ext = nc_handle_extent(handles, m);
+    if (!ext) return DHTGPU_EINVAL;   // nothing applied
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    if (int r = sr_state_extent(c, ext)) return r;
+    const size_t sz[] = {(size_t)m * 4, (size_t)m};
+    uint8_t* p[2];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    DHT_TRY(hipMemcpyAsync(p[0], handles, sz[0], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(hipMemcpyAsync(p[1], val, sz[1], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(launch_sr_state_set(c->sr.st.as<uint8_t>(), reinterpret_cast<uint32_t*>(p[0]), p[1], m, c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_set_candidate(dhtgpu_ctx* c, const uint32_t* slots, const uint32_t* handles, const uint8_t* val,
+                            uint32_t m) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && (!handles || !val)) return DHTGPU_EINVAL;
+    if (int r = sr_check_slots(c, slots, m, false)) return r;
+    if (!nc_handle_extent(handles, m)) return DHTGPU_EINVAL;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const size_t sz[] = {(size_t)m * 4, (size_t)m * 4, (size_t)m};
+    uint8_t* p[3];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    if (int r = sr_upload_slots(c, p[0], slots, m)) return r;
+    DHT_TRY(hipMemcpyAsync(p[1], handles, sz[1], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(hipMemcpyAsync(p[2], val, sz[2], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(launch_sr_candidate(c->sr.view(), reinterpret_cast<uint32_t*>(p[0]), reinterpret_cast<uint32_t*>(p[1]), p[2],
+                                m, c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_insert_dev(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, const uint64_t* ins_off,
+                         const uint32_t* ins_handle, const uint32_t* id_planes, uint64_t id_stride,
+                         const uint8_t* ins_token, uint8_t* ins_added, void* stream) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && (!ins_off || !ins_handle || !id_planes)) return DHTGPU_EINVAL;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_sr_insert(c->sr.view(), slots, m, ins_off, ins_handle, id_planes, id_stride, ins_token, ins_added,
+                             nullptr, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_insert(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, const uint64_t* ins_off,
+                     const uint32_t* ins_handle, const uint8_t* ins_ids20, const uint8_t* ins_token,
+                     uint8_t* ins_added) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && !ins_off) return DHTGPU_EINVAL;
+    if (!m) return DHTGPU_OK;
+    for (uint32_t j = 0; j < m; ++j)
+        if (ins_off[j + 1] < ins_off[j]) return DHTGPU_EINVAL;
+    const uint64_t tot = ins_off[m];
+    if (tot >= 0xFFFFFFFFull) return DHTGPU_ERANGE;
+    if (tot && (!ins_handle || !ins_ids20)) return DHTGPU_EINVAL;
+    if (!nc_handle_extent(ins_handle, tot)) return DHTGPU_EINVAL;
+    if (int r = sr_check_slots(c, slots, m, true)) return r;
+    DHT_TRY(c->bind());
+    const uint64_t is = pad_q((uint32_t)(tot ? tot : 1));
+    // slots | offsets | handles | id planes | tokens | added | overflow word
+    const size_t sz[] = {(size_t)m * 4, ((size_t)m + 1) * 8, (size_t)tot * 4, (size_t)is * 5 * 4, (size_t)tot,
+                         (size_t)tot, 4};
+    uint8_t* p[7];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    if (int r = sr_upload_slots(c, p[0], slots, m)) return r;
+    DHT_TRY(hipMemcpyAsync(p[1], ins_off, sz[1], hipMemcpyHostToDevice, c->stream));
+    if (tot) {
+        DHT_TRY(hipMemcpyAsync(p[2], ins_handle, sz[2], hipMemcpyHostToDevice, c->stream));
+        if (ins_token) DHT_TRY(hipMemcpyAsync(p[4], ins_token, sz[4], hipMemcpyHostToDevice, c->stream));
+        if (int r = upload_ids(c, ins_ids20, tot, reinterpret_cast<uint32_t*>(p[3]), is)) return r;
+    }
+    DHT_TRY(hipMemsetAsync(p[6], 0, 4, c->stream));
+    DHT_TRY(launch_sr_insert(c->sr.view(), reinterpret_cast<uint32_t*>(p[0]), m, reinterpret_cast<uint64_t*>(p[1]),
+                             reinterpret_cast<uint32_t*>(p[2]), reinterpret_cast<uint32_t*>(p[3]), is,
+                             ins_token ? p[4] : nullptr, p[5], reinterpret_cast<uint32_t*>(p[6]), c->stream));
+    if (tot && ins_added) DHT_TRY(hipMemcpyAsync(ins_added, p[5], sz[5], hipMemcpyDeviceToHost, c->stream));
+    return sr_finish(c, reinterpret_cast<uint32_t*>(p[6]));
+}
+
+int dhtgpu_sr_refill_dev(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t count, uint32_t* out_inserted,
+                         void* stream) {
+    if (!c || count == 0 || count > DHTGPU_MAX_K || (m && (!slots || !out_inserted))) return DHTGPU_EINVAL;
+    if (!c->sr.valid || !c->nc.valid) return DHTGPU_ENOIDS;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_sr_refill(c->sr.view(), c->nc.view(), slots, m, count, out_inserted, nullptr, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_refill(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t count, uint32_t* out_inserted) {
+    if (!c || count == 0 || count > DHTGPU_MAX_K || (m && (!slots || !out_inserted))) return DHTGPU_EINVAL;
+    if (!c->sr.valid || !c->nc.valid) return DHTGPU_ENOIDS;
+    if (int r = sr_check_slots(c, slots, m, true)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const size_t sz[] = {(size_t)m * 4, (size_t)m * 4, 4};   // slots | inserted | overflow word
+    uint8_t* p[3];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    if (int r = sr_upload_slots(c, p[0], slots, m)) return r;
+    DHT_TRY(hipMemsetAsync(p[2], 0, 4, c->stream));
+    DHT_TRY(launch_sr_refill(c->sr.view(), c->nc.view(), reinterpret_cast<uint32_t*>(p[0]), m, count,
+                             reinterpret_cast<uint32_t*>(p[1]), reinterpret_cast<uint32_t*>(p[2]), c->stream));
+    DHT_TRY(hipMemcpyAsync(out_inserted, p[1], sz[1], hipMemcpyDeviceToHost, c->stream));
+    return sr_finish(c, reinterpret_cast<uint32_t*>(p[2]));
+}
+
+int dhtgpu_sr_status_dev(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t* out4, void* stream) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && !out4) return DHTGPU_EINVAL;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_sr_status(c->sr.view(), slots, m, out4, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_status(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t* out4) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && !out4) return DHTGPU_EINVAL;
+    if (int r = sr_check_slots(c, slots, m, false)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const size_t sz[] = {(size_t)m * 4, (size_t)m * 16};
+    uint8_t* p[2];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    if (int r = sr_upload_slots(c, p[0], slots, m)) return r;
+    DHT_TRY(launch_sr_status(c->sr.view(), reinterpret_cast<uint32_t*>(p[0]), m, reinterpret_cast<uint32_t*>(p[1]),
+                             c->stream));
+    DHT_TRY(hipMemcpyAsync(out4, p[1], sz[1], hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_lists_dev(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
+                        uint32_t* out_len, void* stream) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && !out_handle) return DHTGPU_EINVAL;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_sr_lists(c->sr.view(), slots, m, out_handle, out_flags, out_len, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_sr_lists(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
+                    uint32_t* out_len) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && !out_handle) return DHTGPU_EINVAL;
+    if (int r = sr_check_slots(c, slots, m, false)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const size_t sz[] = {(size_t)m * 4, (size_t)m * DHTGPU_SR_CAP * 4, (size_t)m * DHTGPU_SR_CAP, (size_t)m * 4};
+    uint8_t* p[4];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    if (int r = sr_upload_slots(c, p[0], slots, m)) return r;
+    DHT_TRY(launch_sr_lists(c->sr.view(), reinterpret_cast<uint32_t*>(p[0]), m, reinterpret_cast<uint32_t*>(p[1]), p[2],
+                            reinterpret_cast<uint32_t*>(p[3]), c->stream));
+    DHT_TRY(hipMemcpyAsync(out_handle, p[1], sz[1], hipMemcpyDeviceToHost, c->stream));
+    if (out_flags) DHT_TRY(hipMemcpyAsync(out_flags, p[2], sz[2], hipMemcpyDeviceToHost, c->stream));
+    if (out_len) DHT_TRY(hipMemcpyAsync(out_len, p[3], sz[3], hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    return DHTGPU_OK;
 }
 
 // ---- f3: crawl replay (iterative searches over a synthetic network) ----------------------

@@ -295,6 +295,39 @@ hipError_t launch_nc_handles(const uint32_t* perm, const uint32_t* hin, uint32_t
 hipError_t launch_nc_bits_set(uint32_t* bits, const uint32_t* handles, const uint8_t* val, uint32_t m, hipStream_t s);
 hipError_t launch_nc_bits_pack(const uint8_t* bytes, uint32_t nh, uint32_t* bits, hipStream_t s);
 
+// rsearch.hip: K10w, the resident searches (dhtgpu_sr_*).  The search set as the kernels see it:
+// device pointers into the context's buffers.
+struct SrView {
+    uint32_t nslots;
+    uint32_t* ep;            // six entry planes, ep[w * es + slot * 64 + l]: the five words of entry l's
+    uint64_t es;             //   distance to the slot's target, then its handle | flags << 28; es = nslots * 64
+    uint32_t* tp;            // target word planes, tp[w * nslots + slot]
+    uint32_t* len;           // [nslots] list lengths (<= 64)
+    uint8_t* bits;           // [nslots] bit0 Search::expired, bit1 overflowed
+    const uint8_t* st;       // node state by handle (bit0 isExpired(), bit1 isRemovable(now)), [nst]
+    uint32_t nst;            //   a handle at or past nst reads as 0
+};
+// Search::insertNode + removeExpiredNode: slot slots[j] takes insertions [ins_off[j], ins_off[j + 1])
+// in order -- handles, id planes ip / is, token bytes (nullable: none) -- added[] (nullable) =
+// insertNode's results; *over_any (nullable) |= 1 when a list overflowed in this call.  Device arrays.
+hipError_t launch_sr_insert(const SrView& v, const uint32_t* slots, uint32_t m, const uint64_t* ins_off,
+                            const uint32_t* ins_handle, const uint32_t* ip, uint64_t is, const uint8_t* tok,
+                            uint8_t* added, uint32_t* over_any, hipStream_t s);
+// Dht::refill: getCachedNodes(the slot's target, count) over nc, each result inserted without a token
+hipError_t launch_sr_refill(const SrView& v, const NcView& nc, const uint32_t* slots, uint32_t m, uint32_t count,
+                            uint32_t* out_inserted, uint32_t* over_any, hipStream_t s);
+hipError_t launch_sr_open(const SrView& v, const uint32_t* slots, const uint32_t* tp, uint64_t ts, uint32_t m,
+                          hipStream_t s);
+hipError_t launch_sr_expire(const SrView& v, const uint32_t* slots, uint32_t m, hipStream_t s);
+hipError_t launch_sr_candidate(const SrView& v, const uint32_t* slots, const uint32_t* handles, const uint8_t* val,
+                               uint32_t m, hipStream_t s);
+// out4[j] = {len, bad nodes, leading bad nodes, bits}; the rows as handles / flags (64 per slot, DHT_NONE padded)
+hipError_t launch_sr_status(const SrView& v, const uint32_t* slots, uint32_t m, uint32_t* out4, hipStream_t s);
+hipError_t launch_sr_lists(const SrView& v, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
+                           uint32_t* out_len, hipStream_t s);
+// st[handles[j]] = val[j], j < m (device arrays, handles inside the array)
+hipError_t launch_sr_state_set(uint8_t* st, const uint32_t* handles, const uint8_t* val, uint32_t m, hipStream_t s);
+
 // crawl.hip: crawl-replay model (iterative searches over implicit routing tables)
 uint32_t search_list_cap();
 // sorts the K4 index buckets (index workspace, n ids, B bits) by (w0, index) into out[n]

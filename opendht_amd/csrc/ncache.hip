@@ -45,16 +45,14 @@
 // kept key) stays in L2.  No radix pass touches the resident keys.
 #include "dhtgpu_dev.h"
 #include "dhtgpu_internal.h"
+#include "nc_walk_dev.h"
 
 namespace dhtgpu {
 namespace {
 
 constexpr uint32_t kNcWaves = 4;   // targets per 256-thread workgroup
 
-__device__ __forceinline__ uint32_t nc_lane(uint32_t x, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)l);
-}
-
+// (the lower bound, the windows and the walk: nc_walk_dev.h, shared with k_sr_refill)
 __global__ __launch_bounds__(256) void k_nc(NcView v, const uint32_t* __restrict__ tp, uint64_t ts, uint32_t q,
                                             uint32_t count, uint32_t* __restrict__ out_h,
                                             uint32_t* __restrict__ out_cnt) {
@@ -64,111 +62,10 @@ __global__ __launch_bounds__(256) void k_nc(NcView v, const uint32_t* __restrict
     uint32_t t[DHT_W];
 #pragma unroll
     for (int w = 0; w < DHT_W; ++w) t[w] = tp[(uint64_t)w * ts + qi];
-    const uint32_t n = v.n;
-
-    // lower bound: the first key >= t lies in [lo, hi]
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 64) {
-        const uint32_t step = (uint32_t)(((uint64_t)(hi - lo) + 63) >> 6);   // >= 2
-        const uint64_t p = (uint64_t)lo + (uint64_t)(lane + 1) * step - 1;
-        bool lt = false;
-        if (p < hi) {
-            uint32_t k[DHT_W];
-            load_id(v.kp, v.ks, p, k);
-            lt = lex_lt(k, t);
-        }
-        const uint32_t c = (uint32_t)__popcll(__ballot(lt));   // pivots below t: a prefix of the lanes
-        const uint64_t nlo = (uint64_t)lo + (uint64_t)c * step;   // pivot c - 1 is below t
-        const uint64_t pc = nlo + step - 1;                       // pivot c is not, when it exists
-        if (pc < hi) hi = (uint32_t)pc;
-        lo = (uint32_t)nlo;   // <= hi: the range shrinks to less than `step` keys
-    }
-    uint32_t lb;
-    {
-        const uint64_t i = (uint64_t)lo + lane;
-        bool lt = false;
-        if (i < hi) {
-            uint32_t k[DHT_W];
-            load_id(v.kp, v.ks, i, k);
-            lt = lex_lt(k, t);
-        }
-        lb = lo + (uint32_t)__popcll(__ballot(lt));
-    }
-    lb = __builtin_amdgcn_readfirstlane(lb);
-
-    // the two windows: distances (key ^ t), handles, accept ballots
-    uint32_t nd[DHT_W], pd[DHT_W], nh = DHT_NONE, ph = DHT_NONE;
-    uint64_t nacc = 0, pacc = 0;
-#pragma unroll
-    for (int w = 0; w < DHT_W; ++w) nd[w] = pd[w] = 0;
-    auto load_next = [&](uint32_t base) {   // lane l: key base + l
-        const uint64_t i = (uint64_t)base + lane;
-        bool a = false;
-        if (i < n) {
-#pragma unroll
-            for (int w = 0; w < DHT_W; ++w) nd[w] = v.kp[(uint64_t)w * v.ks + i] ^ t[w];
-            nh = v.hp[i];
-            a = (v.bits[nh >> 5] >> (nh & 31u)) & 1u;
-        }
-        nacc = __ballot(a);
-    };
-    auto load_prev = [&](uint32_t base) {   // lane l: key base - 1 - l
-        bool a = false;
-        if (lane < base) {
-            const uint32_t i = base - 1 - lane;
-#pragma unroll
-            for (int w = 0; w < DHT_W; ++w) pd[w] = v.kp[(uint64_t)w * v.ks + i] ^ t[w];
-            ph = v.hp[i];
-            a = (v.bits[ph >> 5] >> (ph & 31u)) & 1u;
-        }
-        pacc = __ballot(a);
-    };
-    uint32_t pn = lb, pp = lb;   // the next side's cursor; keys left on the previous side
-    uint32_t nb = pn, pb = pp;   // the windows' bases
-    load_next(nb);
-    load_prev(pb);
-
-    uint32_t c = 0, outv = DHT_NONE;
-    while (c < count) {
-        const bool has_n = pn < n, has_p = pp > 0;
-        if (!has_n && !has_p) break;
-        if (has_n && pn - nb == 64) {
-            nb = pn;
-            load_next(nb);
-        }
-        if (has_p && pb - pp == 64) {
-            pb = pp;
-            load_prev(pb);
-        }
-        const uint32_t ln = (pn - nb) & 63u, lp = (pb - pp) & 63u;
-        bool take_p = !has_n;
-        if (has_n && has_p) {   // InfoHash::xorCmp(prev, next) < 0 (keys are unique: no tie)
-            bool decided = false;
-#pragma unroll
-            for (int w = 0; w < DHT_W; ++w) {
-                const uint32_t a = nc_lane(pd[w], lp), b = nc_lane(nd[w], ln);
-                if (!decided && a != b) {
-                    take_p = a < b;
-                    decided = true;
-                }
-            }
-        }
-        uint32_t h;
-        bool acc;
-        if (take_p) {
-            h = nc_lane(ph, lp);
-            acc = (pacc >> lp) & 1u;
-            --pp;
-        } else {
-            h = nc_lane(nh, ln);
-            acc = (nacc >> ln) & 1u;
-            ++pn;
-        }
-        if (acc) {
-            if (lane == c) outv = h;
-            ++c;
-        }
-    }
+    uint32_t outv = DHT_NONE;   // lane c: the c-th accepted key's handle
+    const uint32_t c = nc_walk<false>(v, nullptr, 0, t, count, lane, [&](uint32_t ci, const uint32_t*, uint32_t h, uint32_t) {
+        if (lane == ci) outv = h;
+    });
     if (lane < count) out_h[(uint64_t)qi * count + lane] = outv;
     if (lane == 0) out_cnt[qi] = c;
 }
