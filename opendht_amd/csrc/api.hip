@@ -474,6 +474,35 @@ static int upload_ids(dhtgpu_ctx* c, const uint8_t* ids20, uint64_t n, uint32_t*
     return DHTGPU_OK;
 }
 
+// An indexed update's arguments: m indices and m bytes (host) laid into buf and copied in on the
+// context's stream; d_idx / d_val = where they are.  The caller owns buf and the synchronisation.
+static int stage_idx_val(dhtgpu_ctx* c, DevBuf& buf, const uint32_t* idx, const uint8_t* val, uint64_t m,
+                         const uint32_t** d_idx, const uint8_t** d_val) {
+    const size_t sz[] = {(size_t)m * 4, (size_t)m};
+    uint8_t* p[2];
+    DHT_TRY(carve(buf, sz, p));
+    DHT_TRY(hipMemcpyAsync(p[0], idx, sz[0], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(hipMemcpyAsync(p[1], val, sz[1], hipMemcpyHostToDevice, c->stream));
+    *d_idx = reinterpret_cast<const uint32_t*>(p[0]);
+    *d_val = p[1];
+    return DHTGPU_OK;
+}
+
+// A by-handle array grown to hold `need` bytes: geometrically from `floor`, bounded by `most`; its
+// first `live` bytes kept and the rest 0, on the context's stream.  The buffer it replaces is parked
+// in `old` until the next growth, for calls in flight on other streams.
+static int grow_kept(dhtgpu_ctx* c, DevBuf& cur, DevBuf& old, size_t live, size_t need, size_t floor, size_t most) {
+    if (need <= cur.cap) return DHTGPU_OK;
+    const size_t cap = std::min(std::max(need, std::max(2 * cur.cap, floor)), most);
+    DevBuf nb;
+    DHT_TRY(nb.ensure(cap));
+    if (live) DHT_TRY(hipMemcpyAsync(nb.p, cur.p, live, hipMemcpyDeviceToDevice, c->stream));
+    DHT_TRY(hipMemsetAsync(nb.as<uint8_t>() + live, 0, cap - live, c->stream));
+    old = std::move(cur);   // (old's previous buffer goes with nb)
+    cur = std::move(nb);
+    return DHTGPU_OK;
+}
+
 // The ids of a set that carry a prefix, in two passes over scratch carved from the context's aux:
 // count() (one host sync for the total, which sizes the caller's output), then compact().
 namespace {
@@ -805,11 +834,10 @@ int dhtgpu_update_accept(dhtgpu_ctx* c, const uint32_t* idx, const uint8_t* val,
         DHT_TRY(launch_fill(c->acc.bits.as<uint32_t>(), (c->n + 31) / 32, 0xFFFFFFFFu, s));
         DHT_TRY(launch_view_trim(c->acc.bits.as<uint32_t>(), c->n, s));
     }
-    const size_t ib = al256((size_t)m * 4);
-    DHT_TRY(c->staging.ensure(ib + (size_t)m));
-    DHT_TRY(hipMemcpyAsync(c->staging.p, idx, (size_t)m * 4, hipMemcpyHostToDevice, s));
-    DHT_TRY(hipMemcpyAsync(c->staging.as<uint8_t>() + ib, val, (size_t)m, hipMemcpyHostToDevice, s));
-    DHT_TRY(launch_view_update(c->acc.bits.as<uint32_t>(), c->staging.as<uint32_t>(), c->staging.as<uint8_t>() + ib, m, s));
+    const uint32_t* d_idx;
+    const uint8_t* d_val;
+    if (int r = stage_idx_val(c, c->staging, idx, val, m, &d_idx, &d_val)) return r;
+    DHT_TRY(launch_bits_update(c->acc.bits.as<uint32_t>(), d_idx, d_val, m, s));
     DHT_TRY(hipStreamSynchronize(s));   // idx / val are the caller's again
     c->acc.has_mask = true;
     c->acc.stale = true;
@@ -1942,11 +1970,10 @@ int dhtgpu_rt_update_good(dhtgpu_ctx* c, const uint32_t* idx, const uint8_t* val
         if (idx[j] >= c->rt.v.nn) return DHTGPU_EINVAL;   // nothing applied
     if (!m) return DHTGPU_OK;
     DHT_TRY(c->bind());
-    const size_t ib = al256((size_t)m * 4);
-    DHT_TRY(c->staging.ensure(ib + (size_t)m));
-    DHT_TRY(hipMemcpyAsync(c->staging.p, idx, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
-    DHT_TRY(hipMemcpyAsync(c->staging.as<uint8_t>() + ib, val, (size_t)m, hipMemcpyHostToDevice, c->stream));
-    DHT_TRY(launch_rt_good_set(c->rt.good, c->staging.as<uint32_t>(), c->staging.as<uint8_t>() + ib, m, c->stream));
+    const uint32_t* d_idx;
+    const uint8_t* d_val;
+    if (int r = stage_idx_val(c, c->staging, idx, val, m, &d_idx, &d_val)) return r;
+    DHT_TRY(launch_bytes_update(c->rt.good, d_idx, d_val, m, true, c->stream));
     DHT_TRY(launch_rt_gpre(c->rt.v, c->rt.gpre, c->stream));
     return DHTGPU_OK;
 }
@@ -2029,17 +2056,10 @@ int dhtgpu_rt_closer(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t cou
 // stream.  The mask it replaces is kept until the next growth, for lookups in flight on other streams.
 static int nc_mask_ensure(dhtgpu_ctx* c, uint64_t nh) {
     dhtgpu_ctx::NCache& t = c->nc;
-    const uint64_t need = (nh + 31) / 32;
-    if (need <= t.words) return DHTGPU_OK;
-    const uint64_t w = std::min<uint64_t>(std::max<uint64_t>(need, std::max<uint64_t>(2 * t.words, 1024)),
-                                          DHTGPU_NC_MAX_HANDLE / 32);
-    DevBuf nb;
-    DHT_TRY(nb.ensure((size_t)w * 4));
-    if (t.words) DHT_TRY(hipMemcpyAsync(nb.p, t.bits.p, (size_t)t.words * 4, hipMemcpyDeviceToDevice, c->stream));
-    DHT_TRY(hipMemsetAsync(nb.as<uint32_t>() + t.words, 0, (size_t)(w - t.words) * 4, c->stream));
-    t.bits_old = std::move(t.bits);   // (bits_old's previous buffer goes with nb)
-    t.bits = std::move(nb);
-    t.words = w;
+    if (int r = grow_kept(c, t.bits, t.bits_old, (size_t)t.words * 4, (size_t)((nh + 31) / 32) * 4, 1024 * 4,
+                          DHTGPU_NC_MAX_HANDLE / 32 * 4))
+        return r;
+    t.words = t.bits.cap / 4;
     return DHTGPU_OK;
 }
 
@@ -2190,11 +2210,10 @@ int dhtgpu_nc_update_accept(dhtgpu_ctx* c, const uint32_t* handles, const uint8_
     DHT_TRY(c->bind());
     dhtgpu_ctx::NCache& t = c->nc;
     if (int r = nc_mask_ensure(c, ext)) return r;
-    DHT_TRY(t.hin.ensure((size_t)m * 4));
-    DHT_TRY(t.ain.ensure((size_t)m));
-    DHT_TRY(hipMemcpyAsync(t.hin.p, handles, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
-    DHT_TRY(hipMemcpyAsync(t.ain.p, val, (size_t)m, hipMemcpyHostToDevice, c->stream));
-    DHT_TRY(launch_nc_bits_set(t.bits.as<uint32_t>(), t.hin.as<uint32_t>(), t.ain.as<uint8_t>(), m, c->stream));
+    const uint32_t* d_idx;
+    const uint8_t* d_val;
+    if (int r = stage_idx_val(c, t.hin, handles, val, m, &d_idx, &d_val)) return r;
+    DHT_TRY(launch_bits_update(t.bits.as<uint32_t>(), d_idx, d_val, m, c->stream));
     return DHTGPU_OK;
 }
 
@@ -2276,15 +2295,8 @@ static int sr_check_slots(const dhtgpu_ctx* c, const uint32_t* slots, uint32_t m
 static int sr_state_extent(dhtgpu_ctx* c, uint64_t nh) {
     dhtgpu_ctx::Searches& t = c->sr;
     if (nh <= t.nst) return DHTGPU_OK;
-    if (nh > t.st.cap) {
-        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(nh, std::max<uint64_t>(2 * t.st.cap, 4096)),
-                                                DHTGPU_NC_MAX_HANDLE);
-        DevBuf nb;
-        DHT_TRY(nb.ensure((size_t)cap));
-        if (t.nst) DHT_TRY(hipMemcpyAsync(nb.p, t.st.p, t.nst, hipMemcpyDeviceToDevice, c->stream));
-        t.st_old = std::move(t.st);   // (st_old's previous buffer goes with nb)
-        t.st = std::move(nb);
-    }
+    if (int r = grow_kept(c, t.st, t.st_old, t.nst, (size_t)nh, 4096, DHTGPU_NC_MAX_HANDLE)) return r;
+    // (an array that did not grow may hold bytes of an extent dhtgpu_sr_set_state dropped)
     DHT_TRY(hipMemsetAsync(t.st.as<uint8_t>() + t.nst, 0, (size_t)(nh - t.nst), c->stream));
     t.nst = (uint32_t)nh;
     return DHTGPU_OK;
@@ -2380,12 +2392,10 @@ int dhtgpu_sr_update_state(dhtgpu_ctx* c, const uint32_t* handles, const uint8_t
     if (!m) return DHTGPU_OK;
     DHT_TRY(c->bind());
     if (int r = sr_state_extent(c, ext)) return r;
-    const size_t sz[] = {(size_t)m * 4, (size_t)m};
-    uint8_t* p[2];
-    DHT_TRY(carve(c->sr.io, sz, p));
-    DHT_TRY(hipMemcpyAsync(p[0], handles, sz[0], hipMemcpyHostToDevice, c->stream));
-    DHT_TRY(hipMemcpyAsync(p[1], val, sz[1], hipMemcpyHostToDevice, c->stream));
-    DHT_TRY(launch_sr_state_set(c->sr.st.as<uint8_t>(), reinterpret_cast<uint32_t*>(p[0]), p[1], m, c->stream));
+    const uint32_t* d_idx;
+    const uint8_t* d_val;
+    if (int r = stage_idx_val(c, c->sr.io, handles, val, m, &d_idx, &d_val)) return r;
+    DHT_TRY(launch_bytes_update(c->sr.st.as<uint8_t>(), d_idx, d_val, m, false, c->stream));
     return DHTGPU_OK;
 }
 

@@ -37,6 +37,7 @@
 // This file holds the kernels and what calls HIP.  The plan of a call, its workspace layout and
 // every decision of a launch are host-only code in batch_plan.cpp (decide_batch); batch_plan.h
 // holds the constants and structures both sides share.
+#include "prims_dev.h"
 #include "scan_dev.h"
 #include <hip/hip_ext.h>
 
@@ -64,19 +65,6 @@ __device__ __forceinline__ uint32_t top_bits(uint32_t w, uint32_t b) { return b 
 // stores before the kernel ends.
 __device__ __forceinline__ void sync_lds() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// Inclusive scan over the 64 lanes of a wave with DPP (no LDS): row_shr 1/2/4/8 inside each
-// 16-lane row, then row_bcast 15 / 31 across rows.  Lanes whose DPP source is out of range
-// take `old` = 0.  Needs the whole wave active.
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);   // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);   // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);   // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);   // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return x;
 }
 
 // Exclusive scan of a[0, len) in LDS by a block of NT threads; returns the total.  Every

@@ -25,6 +25,18 @@ inline hipError_t per_device_once(std::once_flag* flags, void (*set)()) {
     return hipSuccess;
 }
 
+// prims.hip: the primitives every family shares (their device forms: prims_dev.h)
+// Exclusive scan of `rows` consecutive rows of len words each, in -> out (out == in: in place), one
+// workgroup per row; tot[r] = row r's sum, in the width of the caller's slot.  One array is one row.
+hipError_t launch_excl_scan(const uint32_t* in, uint32_t* out, uint32_t rows, uint32_t len, uint32_t* tot, hipStream_t s);
+hipError_t launch_excl_scan(const uint32_t* in, uint32_t* out, uint32_t rows, uint32_t len, unsigned long long* tot,
+                            hipStream_t s);
+// bit idx[j] of bits = val[j] != 0, j < m (device arrays; idx inside the mask, checked by the caller)
+hipError_t launch_bits_update(uint32_t* bits, const uint32_t* idx, const uint8_t* val, uint64_t m, hipStream_t s);
+// bytes[idx[j]] = normalise ? val[j] != 0 : val[j], j < m (device arrays; idx inside the array)
+hipError_t launch_bytes_update(uint8_t* bytes, const uint32_t* idx, const uint8_t* val, uint64_t m, bool normalise,
+                               hipStream_t s);
+
 // keys.hip
 hipError_t launch_gen(uint64_t seed, uint64_t start, uint64_t n, uint32_t* planes,
                       uint64_t stride, hipStream_t s);
@@ -53,8 +65,6 @@ uint64_t view_mask_words(uint64_t stride);
 hipError_t launch_view_pack(const uint8_t* bytes, uint64_t nwords, uint32_t* bits, hipStream_t s);
 // clears the bits past n in the word that holds bit n
 hipError_t launch_view_trim(uint32_t* bits, uint64_t n, hipStream_t s);
-// bit idx[j] = val[j] != 0, j < m (device arrays; idx < n checked by the caller)
-hipError_t launch_view_update(uint32_t* bits, const uint32_t* idx, const uint8_t* val, uint64_t m, hipStream_t s);
 // toff[stride / kTile] = exclusive offsets of the tiles' accepted ids, *d_total = their number
 hipError_t launch_view_count(const uint32_t* bits, uint64_t stride, uint32_t* toff, unsigned long long* d_total,
                              hipStream_t s);
@@ -248,8 +258,6 @@ struct RtView {
 };
 // gpre from off and good (one workgroup; after every change of the good bytes)
 hipError_t launch_rt_gpre(const RtView& v, uint32_t* gpre, hipStream_t s);
-// good[idx[j]] = val[j] != 0, j < m (device arrays; idx < nn checked by the caller)
-hipError_t launch_rt_good_set(uint8_t* good, const uint32_t* idx, const uint8_t* val, uint32_t m, hipStream_t s);
 // findClosestNodes per target over the mirror (1 <= count <= DHTGPU_MAX_K_DEV): indices + counts;
 // the count-8 result as bufferNodes records (out_idx nullable: q x 8); the closeness flag
 // (out_cnt nullable)
@@ -291,8 +299,7 @@ hipError_t launch_nc_erase(const NcView& v, uint32_t* dst, uint64_t ds, const ui
 // hp[j] = hin[perm[j]] with its accept bit set, or perm[j] when hin is null (bits untouched)
 hipError_t launch_nc_handles(const uint32_t* perm, const uint32_t* hin, uint32_t n, uint32_t* hp, uint32_t* bits,
                              hipStream_t s);
-// bit handles[j] = val[j] != 0, j < m; bits [0, nh) from bytes[nh] (device arrays, handles in range)
-hipError_t launch_nc_bits_set(uint32_t* bits, const uint32_t* handles, const uint8_t* val, uint32_t m, hipStream_t s);
+// bits [0, nh) from bytes[nh] (device arrays)
 hipError_t launch_nc_bits_pack(const uint8_t* bytes, uint32_t nh, uint32_t* bits, hipStream_t s);
 
 // rsearch.hip: K10w, the resident searches (dhtgpu_sr_*).  The search set as the kernels see it:
@@ -325,8 +332,6 @@ hipError_t launch_sr_candidate(const SrView& v, const uint32_t* slots, const uin
 hipError_t launch_sr_status(const SrView& v, const uint32_t* slots, uint32_t m, uint32_t* out4, hipStream_t s);
 hipError_t launch_sr_lists(const SrView& v, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
                            uint32_t* out_len, hipStream_t s);
-// st[handles[j]] = val[j], j < m (device arrays, handles inside the array)
-hipError_t launch_sr_state_set(uint8_t* st, const uint32_t* handles, const uint8_t* val, uint32_t m, hipStream_t s);
 
 // crawl.hip: crawl-replay model (iterative searches over implicit routing tables)
 uint32_t search_list_cap();

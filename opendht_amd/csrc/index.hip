@@ -19,6 +19,7 @@
 // the id words 1..4 are read from the resident planes only when two w0 distances tie.
 #include "dhtgpu_dev.h"
 #include "dhtgpu_internal.h"
+#include "prims_dev.h"
 
 #include <mutex>
 
@@ -31,8 +32,9 @@ constexpr int kBlk = 256;
 // no global atomics:
 //   P0  per block (8192 ids): LDS histogram of the top b1 bits -> column of H[bin][block]
 //   P0r one block per bin: exclusive scan of H's row (offsets of each block inside the
-//       bin) and the bin total
-//   P0s one block: exclusive scan of the bin totals -> partition starts (pstart)
+//       bin) and the bin total  (launch_excl_scan, prims.hip)
+//   P0s one block: exclusive scan of the bin totals -> partition starts (pstart); their
+//       sum, n, closes the directory
 //   P1  per block: scatter every id to pstart[bin] + H[bin][block] + LDS rank as an
 //       8-byte entry {w0, idx}
 //   P2  one block per partition: LDS histogram of the next b2 bits -> directory entries
@@ -44,6 +46,7 @@ constexpr int kBlk = 256;
 // candidates by (distance, index), so results do not depend on it.
 constexpr uint32_t kP1Tile = 8192;   // minimum ids per P0/P1 block (256 threads x 32); grown so nblk <= 2048
 constexpr int kP2Blk = 1024;
+constexpr uint32_t kP2Wsum = kP2Blk / 64 + 1;   // block_scan_array's scratch
 constexpr int kP2Per = 16;          // entries per thread per batch: a ~16K partition is one batch
 constexpr uint32_t kLdsMax = 160 * 1024;
 
@@ -70,81 +73,24 @@ __global__ __launch_bounds__(kBlk) void k_p0_hist(const uint32_t* __restrict__ w
     for (uint32_t i = threadIdx.x; i < nbin; i += kBlk) H[(uint64_t)i * nblk + blockIdx.x] = sh[i];
 }
 
-// exclusive scan of `len` values in place (single block of 1024 threads); returns total
-__device__ uint32_t block_scan_inplace(uint32_t* __restrict__ a, uint32_t len, uint32_t* scr) {
-    uint32_t carry = 0;
-    for (uint32_t b = 0; b < len; b += 1024) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t v = i < len ? a[i] : 0;
-        scr[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t o = 1; o < 1024; o <<= 1) {
-            const uint32_t x = threadIdx.x >= o ? scr[threadIdx.x - o] : 0;
-            __syncthreads();
-            scr[threadIdx.x] += x;
-            __syncthreads();
-        }
-        if (i < len) a[i] = carry + scr[threadIdx.x] - v;
-        carry += scr[1023];
-        __syncthreads();
-    }
-    return carry;
-}
-
-// exclusive scan of `len` values in place by a block of NT threads; returns the total
-template <int NT>
-__device__ uint32_t block_scan_nt(uint32_t* __restrict__ a, uint32_t len, uint32_t* scr) {
-    uint32_t carry = 0;
-    for (uint32_t b = 0; b < len; b += NT) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t v = i < len ? a[i] : 0;
-        scr[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t o = 1; o < (uint32_t)NT; o <<= 1) {
-            const uint32_t x = threadIdx.x >= o ? scr[threadIdx.x - o] : 0;
-            __syncthreads();
-            scr[threadIdx.x] += x;
-            __syncthreads();
-        }
-        if (i < len) a[i] = carry + scr[threadIdx.x] - v;
-        carry += scr[NT - 1];
-        __syncthreads();
-    }
-    return carry;
-}
-
-__global__ __launch_bounds__(1024) void k_p0_rowscan(uint32_t* __restrict__ H, uint32_t nblk,
-                                                    uint32_t* __restrict__ pcount) {
-    __shared__ uint32_t scr[1024];
-    const uint32_t total = block_scan_inplace(H + (uint64_t)blockIdx.x * nblk, nblk, scr);
-    if (threadIdx.x == 0) pcount[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void k_p0_scan(uint32_t* __restrict__ pcount, uint32_t nbin,
-                                                 uint32_t* __restrict__ pstart, uint64_t n) {
-    __shared__ uint32_t scr[1024];
-    for (uint32_t i = threadIdx.x; i < nbin; i += 1024) pstart[i] = pcount[i];
-    __syncthreads();
-    block_scan_inplace(pstart, nbin, scr);
-    if (threadIdx.x == 0) pstart[nbin] = (uint32_t)n;
-}
-
 // P1: the block's tile is counting-sorted by partition in LDS first, so that every
 // partition run is then written to HBM contiguously by consecutive lanes (runs are
 // short -- tile / 2^b1 entries -- and scattered 8-byte stores would leave partial lines).
 constexpr uint32_t kP1Stage = 8192;   // entries staged in LDS per round (64 KB)
+constexpr uint32_t kP1Wsum = 8;       // block_scan_array's scratch (kBlk / 64 + 1 words), the stage kept 8-B aligned
+static_assert(kP1Wsum >= kBlk / 64 + 1 && kP1Wsum % 2 == 0, "kP1Wsum");
 
 __global__ __launch_bounds__(kBlk) void k_p1_scatter(const uint32_t* __restrict__ w0, uint64_t n, uint32_t b1,
                                                     uint32_t nblk, uint32_t tile, const uint32_t* __restrict__ H,
                                                     const uint32_t* __restrict__ pstart,
                                                     uint2* __restrict__ tmp) {
-    extern __shared__ uint32_t sh[];   // [gbase 2^b1 | lcnt 2^b1 | loff 2^b1 | scan scratch kBlk | stage]
+    extern __shared__ uint32_t sh[];   // [gbase 2^b1 | lcnt 2^b1 | loff 2^b1 | the scan's wave sums | stage]
     const uint32_t nbin = 1u << b1, shift = 32 - b1;
     uint32_t* gbase = sh;
     uint32_t* lcnt = sh + nbin;
     uint32_t* loff = sh + 2 * nbin;
-    uint32_t* scr = sh + 3 * nbin;
-    uint2* stage = reinterpret_cast<uint2*>(scr + kBlk);
+    uint32_t* wsum = sh + 3 * nbin;
+    uint2* stage = reinterpret_cast<uint2*>(wsum + kP1Wsum);
     for (uint32_t i = threadIdx.x; i < nbin; i += kBlk) gbase[i] = pstart[i] + H[(uint64_t)i * nblk + blockIdx.x];
     const uint64_t base0 = (uint64_t)blockIdx.x * tile;
     const uint32_t mt = (uint32_t)(n - base0 < tile ? n - base0 : tile);
@@ -173,11 +119,9 @@ __global__ __launch_bounds__(kBlk) void k_p1_scatter(const uint32_t* __restrict_
             if (j < m) atomicAdd(lcnt + (v[e] >> shift), 1u);
         }
         __syncthreads();
-        for (uint32_t i = threadIdx.x; i < nbin; i += kBlk) loff[i] = lcnt[i];
-        __syncthreads();
-        block_scan_nt<kBlk>(loff, nbin, scr);
-        for (uint32_t i = threadIdx.x; i < nbin; i += kBlk) lcnt[i] = 0;
-        __syncthreads();
+        block_scan_array<kBlk>(lcnt, loff, nbin, wsum);
+        for (uint32_t i = threadIdx.x; i < nbin; i += kBlk) lcnt[i] = 0;   // (the thread's own entries)
+        __syncthreads();   // loff is complete
 #pragma unroll
         for (uint32_t e = 0; e < PER; ++e) {
             const uint32_t j = (e / 4) * 4 * kBlk + 4 * threadIdx.x + (e % 4);
@@ -203,13 +147,13 @@ __global__ __launch_bounds__(kP2Blk) void k_p2_buckets(const uint2* __restrict__
                                                       const uint32_t* __restrict__ pstart, uint32_t b1,
                                                       uint32_t b2, uint32_t perm_cap, uint32_t* __restrict__ dir,
                                                       uint2* __restrict__ pairs, uint64_t n) {
-    extern __shared__ uint32_t sh[];   // [cnt 2^b2 | offsets 2^b2 | scan scratch kP2Blk | perm]
+    extern __shared__ uint32_t sh[];   // [cnt 2^b2 | offsets 2^b2 | the scan's wave sums | perm]
     const uint32_t p = blockIdx.x;
     const uint32_t nsub = 1u << b2, shift = 32 - b1 - b2, mask = nsub - 1u;
     uint32_t* cnt = sh;
     uint32_t* off = sh + nsub;
-    uint32_t* scr = sh + 2 * nsub;
-    uint32_t* perm = scr + kP2Blk;
+    uint32_t* wsum = sh + 2 * nsub;
+    uint32_t* perm = wsum + kP2Wsum;
     const uint32_t lo = pstart[p], hi = pstart[p + 1], m = hi - lo;
     constexpr uint32_t BATCH = kP2Blk * kP2Per;
     for (uint32_t i = threadIdx.x; i < nsub; i += kP2Blk) cnt[i] = 0;
@@ -227,10 +171,8 @@ __global__ __launch_bounds__(kP2Blk) void k_p2_buckets(const uint2* __restrict__
             if (b + e * kP2Blk + threadIdx.x < m) atomicAdd(cnt + ((key[e] >> shift) & mask), 1u);
     }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < nsub; i += kP2Blk) off[i] = cnt[i];
-    __syncthreads();
-    block_scan_nt<kP2Blk>(off, nsub, scr);
-    for (uint32_t i = threadIdx.x; i < nsub; i += kP2Blk) {
+    block_scan_array<kP2Blk>(cnt, off, nsub, wsum);
+    for (uint32_t i = threadIdx.x; i < nsub; i += kP2Blk) {   // (the thread's own entries; the barrier below completes off)
         dir[((uint64_t)p << b2) + i] = lo + off[i];
         cnt[i] = 0;
     }
@@ -514,6 +456,8 @@ hipError_t launch_index_build(const uint32_t* planes, uint64_t stride, uint64_t 
     uint32_t* H = reinterpret_cast<uint32_t*>(tmp + n);
     uint32_t* pcount = H + np * (nblk ? nblk : 1);
     uint32_t* pstart = pcount + np;
+    // (both kernels take every LDS word from the dynamic block: a static array on top of kLdsMax
+    // makes the attribute call fail)
     // hipFuncSetAttribute applies to the device current at the call: once per device, from
     // whichever thread gets there first (a plain static flag raced between threads and skipped
     // every device after the first)
@@ -528,21 +472,22 @@ hipError_t launch_index_build(const uint32_t* planes, uint64_t stride, uint64_t 
     if (n) {
         k_p0_hist<<<nblk, kBlk, np * 4, s>>>(planes, n, b1, nblk, p1_tile(n), H);
         if (ev) (void)hipEventRecord(ev[1], s);
-        k_p0_rowscan<<<(uint32_t)np, 1024, 0, s>>>(H, nblk, pcount);
+        if (hipError_t e = launch_excl_scan(H, H, (uint32_t)np, nblk, pcount, s)) return e;
     } else {
         if (ev) (void)hipEventRecord(ev[1], s);
         hipError_t e = hipMemsetAsync(pcount, 0, np * 4, s);
         if (e != hipSuccess) return e;
     }
-    k_p0_scan<<<1, 1024, 0, s>>>(pcount, (uint32_t)np, pstart, n);
+    // the bins' counts sum to n: the scan's total is the directory's last entry, pstart[np]
+    if (hipError_t e = launch_excl_scan(pcount, pstart, 1, (uint32_t)np, pstart + np, s)) return e;
     if (ev) (void)hipEventRecord(ev[2], s);
     if (n)
-        k_p1_scatter<<<nblk, kBlk, (3 * np + kBlk) * 4 + kP1Stage * 8, s>>>(planes, n, b1, nblk, p1_tile(n), H,
+        k_p1_scatter<<<nblk, kBlk, (3 * np + kP1Wsum) * 4 + kP1Stage * 8, s>>>(planes, n, b1, nblk, p1_tile(n), H,
                                                                           pstart, tmp);
     if (ev) (void)hipEventRecord(ev[3], s);
     // LDS: fixed part + a permutation sized 1.25x the average partition + 512 (several
     // blocks per CU); larger partitions (clustered inputs) take the scatter path
-    const uint32_t fixed = ((2u << b2) + kP2Blk) * 4;
+    const uint32_t fixed = ((2u << b2) + kP2Wsum) * 4;
     uint64_t cap = (n >> b1) + (n >> b1) / 4 + 512;
     if (cap > (kLdsMax - fixed) / 4) cap = (kLdsMax - fixed) / 4;
     k_p2_buckets<<<(uint32_t)np, kP2Blk, fixed + (uint32_t)cap * 4, s>>>(tmp, pstart, b1, b2, (uint32_t)cap, dir,

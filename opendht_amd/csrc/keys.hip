@@ -91,28 +91,6 @@ __global__ __launch_bounds__(kBlock) void k_sel_count(const uint32_t* __restrict
     if (threadIdx.x == 0) bcount[blockIdx.x] = c;
 }
 
-__global__ __launch_bounds__(1024) void k_sel_scan(uint32_t* __restrict__ a, uint32_t len,
-                                                   unsigned long long* __restrict__ total) {
-    __shared__ uint32_t scr[1024];
-    uint32_t carry = 0;
-    for (uint32_t b = 0; b < len; b += 1024) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t v = i < len ? a[i] : 0;
-        scr[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t o = 1; o < 1024; o <<= 1) {
-            const uint32_t x = threadIdx.x >= o ? scr[threadIdx.x - o] : 0;
-            __syncthreads();
-            scr[threadIdx.x] += x;
-            __syncthreads();
-        }
-        if (i < len) a[i] = carry + scr[threadIdx.x] - v;
-        carry += scr[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
 // order-preserving compaction: within a block, chunks of 256 ids in index order; a
 // chunk's matches are ranked by wave ballots + per-wave offsets in LDS
 __global__ __launch_bounds__(kBlock) void k_sel_compact(const uint32_t* __restrict__ planes, uint64_t stride,
@@ -160,7 +138,7 @@ hipError_t launch_select_prefix(const uint32_t* planes, uint64_t stride, uint64_
     const uint32_t nblk = (uint32_t)((n + kSelPer - 1) / kSelPer);
     if (!nblk) return hipMemsetAsync(d_total, 0, 8, s);
     k_sel_count<<<nblk, kBlock, 0, s>>>(planes, n, pbits, pval, scratch);
-    k_sel_scan<<<1, 1024, 0, s>>>(scratch, nblk, d_total);
+    if (hipError_t e = launch_excl_scan(scratch, scratch, 1, nblk, d_total, s)) return e;
     if (out) k_sel_compact<<<nblk, kBlock, 0, s>>>(planes, stride, n, pbits, pval, scratch, out, out_stride, gidx, gbase);
     return hipGetLastError();
 }

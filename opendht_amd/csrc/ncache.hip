@@ -3,11 +3,11 @@
 //                   per target, the accepted keys' handles in the reference's walk order
 //   k_nc_rank       a sorted mutation batch against the resident keys: rank, keep flag, result byte,
 //                   kept keys per 256-key block
-//   k_nc_scan       exclusive scan of the blocks' counts + their total (the one host read-back)
 //   k_nc_compact    the kept batch keys' ranks and sources, compacted
 //   k_nc_merge      the resident keys and the kept batch keys into the other buffer set
 //   k_nc_handles    the handle plane of dhtgpu_nc_set (+ the handles' accept bits)
-//   k_nc_bits_set / k_nc_bits_pack   accept bits by handle (update_accept / set_accept)
+//   k_nc_bits_pack  accept bits by handle from bytes (set_accept)
+// The scan of k_nc_rank's block counts and update_accept's bit setter are the shared ones of prims.hip.
 //
 // The mirror is NodeCache::NodeMap (include/opendht/node_cache.h:43) as six u32 planes -- the five
 // key words, lexicographically sorted, and the caller's handle of each key (the map's value) --
@@ -114,36 +114,6 @@ __global__ __launch_bounds__(256) void k_nc_rank(const uint32_t* __restrict__ kp
     if (threadIdx.x == 0) bsum[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 
-// out[b] = in[0] + .. + in[b - 1], *total = their sum: one 1024-thread workgroup (nb = the batch's
-// 256-key blocks: 4 KB per million keys)
-__global__ __launch_bounds__(1024) void k_nc_scan(const uint32_t* __restrict__ in, uint32_t nb,
-                                                  uint32_t* __restrict__ out, uint32_t* __restrict__ total) {
-    __shared__ uint32_t wsum[16];
-    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
-    uint32_t carry = 0;
-    for (uint32_t c0 = 0; c0 < nb; c0 += 1024) {
-        const uint32_t i = c0 + threadIdx.x;
-        const uint32_t v = i < nb ? in[i] : 0u;
-        uint32_t x = v;   // inclusive wave scan
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)x, o);
-            if (lane >= (uint32_t)o) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        uint32_t before = carry, all = 0;
-        for (uint32_t j = 0; j < 16; ++j) {
-            if (j < w) before += wsum[j];
-            all += wsum[j];
-        }
-        if (i < nb) out[i] = before + x - v;
-        carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
 // the kept batch keys' ranks and sources as dense lists: kept key j goes to boff[block] + the kept
 // keys before it in its block (ballots, the waves' counts through LDS)
 __global__ __launch_bounds__(256) void k_nc_compact(const uint32_t* __restrict__ rank, const uint32_t* __restrict__ flag,
@@ -237,14 +207,6 @@ __global__ __launch_bounds__(256) void k_nc_handles(const uint32_t* __restrict__
     atomicOr(bits + (h >> 5), 1u << (h & 31u));
 }
 
-__global__ __launch_bounds__(256) void k_nc_bits_set(uint32_t* __restrict__ bits, const uint32_t* __restrict__ h,
-                                                     const uint8_t* __restrict__ val, uint32_t m) {
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= m) return;
-    if (val[j]) atomicOr(bits + (h[j] >> 5), 1u << (h[j] & 31u));
-    else atomicAnd(bits + (h[j] >> 5), ~(1u << (h[j] & 31u)));
-}
-
 // bits of handles [0, nh) from bytes[nh]; the last word keeps its bits past nh
 __global__ __launch_bounds__(256) void k_nc_bits_pack(const uint8_t* __restrict__ bytes, uint32_t nh,
                                                       uint32_t* __restrict__ bits) {
@@ -276,7 +238,8 @@ hipError_t launch_nc_rank(bool erase, const NcView& v, const uint32_t* bp, uint6
     const uint32_t nb = blocks256(m);
     if (erase) k_nc_rank<true><<<nb, 256, 0, s>>>(v.kp, v.ks, v.n, bp, bs, perm, m, rank, flag, bsum, res);
     else k_nc_rank<false><<<nb, 256, 0, s>>>(v.kp, v.ks, v.n, bp, bs, perm, m, rank, flag, bsum, res);
-    k_nc_scan<<<1, 1024, 0, s>>>(bsum, nb, boff, d_total);
+    // the blocks' counts scanned + their total, the one host read-back (4 KB per million batch keys)
+    if (hipError_t e = launch_excl_scan(bsum, boff, 1, nb, d_total, s)) return e;
     k_nc_compact<<<nb, 256, 0, s>>>(rank, flag, boff, m, kpos, ksrc);
     return hipGetLastError();
 }
@@ -303,12 +266,6 @@ hipError_t launch_nc_handles(const uint32_t* perm, const uint32_t* hin, uint32_t
                              hipStream_t s) {
     if (!n) return hipSuccess;
     k_nc_handles<<<blocks256(n), 256, 0, s>>>(perm, hin, n, hp, bits);
-    return hipGetLastError();
-}
-
-hipError_t launch_nc_bits_set(uint32_t* bits, const uint32_t* handles, const uint8_t* val, uint32_t m, hipStream_t s) {
-    if (!m) return hipSuccess;
-    k_nc_bits_set<<<blocks256(m), 256, 0, s>>>(bits, handles, val, m);
     return hipGetLastError();
 }
 

@@ -4,7 +4,8 @@
 //   k_sr_refill     Dht::refill (src/dht.cpp:656-677): getCachedNodes over the resident NodeCache
 //                   mirror (the walk of nc_walk_dev.h), every accepted key fed straight into the
 //                   insertion -- its distance is already in the window's registers
-//   k_sr_open / k_sr_expire / k_sr_candidate / k_sr_status / k_sr_lists / k_sr_state_set
+//   k_sr_open / k_sr_expire / k_sr_candidate / k_sr_status / k_sr_lists
+// (update_state's byte setter is the shared one of prims.hip)
 //
 // A search lives in a slot.  Its node list is a row of 64 entries in six u32 planes -- the five
 // words of the node's DISTANCE to the search's target (id ^ target), so that an ordering test is a
@@ -341,12 +342,6 @@ __global__ __launch_bounds__(256) void k_sr_lists(SrView v, const uint32_t* __re
     if (out_len && lane == 0) out_len[j] = len;
 }
 
-__global__ __launch_bounds__(256) void k_sr_state_set(uint8_t* __restrict__ st, const uint32_t* __restrict__ h,
-                                                      const uint8_t* __restrict__ val, uint32_t m) {
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j < m) st[h[j]] = val[j];
-}
-
 inline uint32_t wave_blocks(uint32_t m) { return (m + kSrWaves - 1) / kSrWaves; }
 
 }  // namespace
@@ -396,12 +391,6 @@ hipError_t launch_sr_lists(const SrView& v, const uint32_t* slots, uint32_t m, u
                            uint32_t* out_len, hipStream_t s) {
     if (!m) return hipSuccess;
     k_sr_lists<<<wave_blocks(m), 64 * kSrWaves, 0, s>>>(v, slots, m, out_handle, out_flags, out_len);
-    return hipGetLastError();
-}
-
-hipError_t launch_sr_state_set(uint8_t* st, const uint32_t* handles, const uint8_t* val, uint32_t m, hipStream_t s) {
-    if (!m) return hipSuccess;
-    k_sr_state_set<<<(m + 255) / 256, 256, 0, s>>>(st, handles, val, m);
     return hipGetLastError();
 }
 

@@ -7,7 +7,6 @@
 //                    closer    + key.xorCmp(nodes.back()->id, myid) < 0, the closeness test of
 //                              maintainStorage (src/dht.cpp:1862-1879) and onAnnounce (:2293-2294)
 //   k_rt_gpre      prefix sums of the per-bucket good counts (after a change of the good bytes)
-//   k_rt_good_set  good[idx[j]] = val[j]
 //
 // K1r (table.hip) gives one thread a serial, dependent-load walk; that suits 65,536 targets and
 // leaves the machine idle at a responder's batch sizes.  Here one wave64 answers one target, the
@@ -263,12 +262,6 @@ __global__ __launch_bounds__(256) void k_rt_gpre(uint32_t nb, const uint32_t* __
     if (b == 0) gpre[0] = 0;
 }
 
-__global__ __launch_bounds__(256) void k_rt_good_set(uint8_t* __restrict__ good, const uint32_t* __restrict__ idx,
-                                                     const uint8_t* __restrict__ val, uint32_t m) {
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j < m) good[idx[j]] = val[j] != 0;
-}
-
 template <int FORM>
 hipError_t launch_rt(const RtView& v, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t count, const RtOut& o,
                      hipStream_t s) {
@@ -288,12 +281,6 @@ hipError_t launch_rt(const RtView& v, const uint32_t* tp, uint64_t ts, uint32_t 
 
 hipError_t launch_rt_gpre(const RtView& v, uint32_t* gpre, hipStream_t s) {
     k_rt_gpre<<<1, 256, 0, s>>>(v.nb, v.off, v.good, gpre);
-    return hipGetLastError();
-}
-
-hipError_t launch_rt_good_set(uint8_t* good, const uint32_t* idx, const uint8_t* val, uint32_t m, hipStream_t s) {
-    if (!m) return hipSuccess;
-    k_rt_good_set<<<(m + 255) / 256, 256, 0, s>>>(good, idx, val, m);
     return hipGetLastError();
 }
 

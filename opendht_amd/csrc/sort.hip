@@ -10,6 +10,7 @@
 // w0).  One pass = three kernels:
 //   hist     per 4096-id tile, the digit histogram (LDS atomics) -> counts[digit][tile]
 //   rowscan  one workgroup per digit: exclusive scan of its row over the tiles + row total
+//            (launch_excl_scan, prims.hip)
 //   scatter  every tile re-reads its ids in index order, 256 at a time; a wave ranks equal
 //            digits among its lanes with 8 ballots (bit-sliced match), the waves' per-digit
 //            counts go through LDS in wave order, so the scatter is stable; the five key
@@ -45,35 +46,6 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_hist(const uint32_t* __re
     }
     __syncthreads();
     counts[(uint64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// exclusive scan of counts[d][0 .. ntiles) in place; tot[d] = the row's sum
-__global__ __launch_bounds__(1024) void k_sort_rowscan(uint32_t* __restrict__ counts, uint32_t ntiles,
-                                                       uint32_t* __restrict__ tot) {
-    __shared__ uint32_t wsum[16];
-    uint32_t* row = counts + (uint64_t)blockIdx.x * ntiles;
-    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
-    uint32_t carry = 0;
-    for (uint32_t c0 = 0; c0 < ntiles; c0 += 1024) {
-        const uint32_t i = c0 + threadIdx.x;
-        const uint32_t v = i < ntiles ? row[i] : 0u;
-        uint32_t x = v;   // inclusive wave scan
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)x, o);
-            if (lane >= (uint32_t)o) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        uint32_t before = carry;
-        for (uint32_t j = 0; j < w; ++j) before += wsum[j];
-        uint32_t all = 0;
-        for (uint32_t j = 0; j < 16; ++j) all += wsum[j];
-        if (i < ntiles) row[i] = before + x - v;
-        carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
 }
 
 struct SortBufs {
@@ -201,7 +173,7 @@ hipError_t launch_sort_ids(const uint32_t* planes, uint64_t stride, uint64_t n, 
                 }
                 sb.in_stride = sb.out_stride = 0;
                 k_sort_hist<<<ntiles, kSortThreads, 0, s>>>(sb.in[word], n, 8 * byte, ntiles, counts);
-                k_sort_rowscan<<<256, 1024, 0, s>>>(counts, ntiles, tot);
+                if (hipError_t x = launch_excl_scan(counts, counts, 256, ntiles, tot, s)) return x;
                 k_sort_scatter<<<ntiles, kSortThreads, 0, s>>>(sb, n, (uint32_t)word, 8 * byte, ntiles, counts, tot);
             }
         }

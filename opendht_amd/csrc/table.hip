@@ -5,6 +5,7 @@
 //   a8  k_cached       : NodeCache::getCachedNodes (src/node_cache.cpp:42-74)
 #include "dhtgpu_dev.h"
 #include "dhtgpu_internal.h"
+#include "prims_dev.h"
 
 #include <type_traits>
 
@@ -280,9 +281,7 @@ __global__ __launch_bounds__(kClsBlock) void k_classify(
     auto flush_acc = [&]() {   // wave-uniform
 #pragma unroll
         for (uint32_t b = 0; b < kRegT; ++b) {
-            uint32_t x = (uint32_t)(((b & 1u) ? acc_o : acc_e) >> (8 * (b >> 1))) & 0xFFu;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o);
+            const uint32_t x = wave_sum((uint32_t)(((b & 1u) ? acc_o : acc_e) >> (8 * (b >> 1))) & 0xFFu);
             if (lane == 0 && x) atomicAdd(&sh[b], x);
         }
         acc_e = acc_o = 0;

@@ -5,7 +5,7 @@
 // HBM-streaming kernel:
 //   V1 k_view_count    one wave per 4,096-id tile: popcounts of the tile's 128 mask words (n / 8
 //                      bytes read; no id word is read to count)
-//   V2 k_view_scan     exclusive scan of the tile counts (one workgroup) + the total
+//   V2 launch_excl_scan (prims.hip)  exclusive scan of the tile counts (one workgroup) + the total
 //   V3 k_view_compact  one workgroup per tile.  An accepted id's rank is the tile's offset + the
 //                      popcounts of the mask words below it (an LDS prefix over the 128 words, one
 //                      barrier per tile) + the popcount of its own word's lower bits: no ballot,
@@ -17,18 +17,13 @@
 // Algorithmic bytes: 20 n + n / 8 read (less for empty tiles), 24 n_acc written (28 on shards).
 #include "dhtgpu_dev.h"
 #include "dhtgpu_internal.h"
+#include "prims_dev.h"
 
 namespace dhtgpu {
 namespace {
 
 constexpr uint32_t kViewThreads = 256;
 constexpr uint32_t kViewWords = kTile / 32;   // mask words per tile
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // bytes (nonzero = accepted) -> mask words: a lane packs 16 bytes, lane pairs make a word.
 // bytes: 32 * nwords of them (the caller zero-pads past n)
@@ -53,16 +48,6 @@ __global__ void k_view_trim(uint32_t* __restrict__ bits, uint64_t n) {
     if (threadIdx.x == 0 && blockIdx.x == 0 && (n & 31)) bits[n >> 5] &= (1u << (n & 31)) - 1u;
 }
 
-__global__ __launch_bounds__(kViewThreads) void k_view_update(uint32_t* __restrict__ bits,
-                                                              const uint32_t* __restrict__ idx,
-                                                              const uint8_t* __restrict__ val, uint64_t m) {
-    for (uint64_t j = (uint64_t)blockIdx.x * kViewThreads + threadIdx.x; j < m; j += (uint64_t)gridDim.x * kViewThreads) {
-        const uint32_t i = idx[j], bit = 1u << (i & 31);
-        if (val[j]) atomicOr(bits + (i >> 5), bit);
-        else atomicAnd(bits + (i >> 5), ~bit);
-    }
-}
-
 __global__ __launch_bounds__(kViewThreads) void k_view_count(const uint2* __restrict__ bits, uint32_t ntiles,
                                                              uint32_t* __restrict__ tcount) {
     const uint32_t tile = blockIdx.x * (kViewThreads / 64) + (threadIdx.x >> 6);
@@ -72,39 +57,10 @@ __global__ __launch_bounds__(kViewThreads) void k_view_count(const uint2* __rest
     if (lane_id() == 0) tcount[tile] = c;
 }
 
-// in-place exclusive scan of a[len], *total = the sum (one workgroup of 1,024)
-__global__ __launch_bounds__(1024) void k_view_scan(uint32_t* __restrict__ a, uint32_t len,
-                                                    unsigned long long* __restrict__ total) {
-    __shared__ uint32_t wtot[16];
-    const uint32_t per = (len + 1023) / 1024;
-    const uint32_t lo = threadIdx.x * per, hi = lo + per < len ? lo + per : len;
-    uint32_t mine = 0;
-    for (uint32_t i = lo; i < hi; ++i) mine += a[i];
-    uint32_t inc = mine;   // inclusive scan over the wave, then over the 16 wave totals
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t x = __shfl_up(inc, o);
-        if (lane_id() >= (uint32_t)o) inc += x;
-    }
-    if (lane_id() == 63) wtot[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint32_t run = inc - mine, all = 0;
-    for (uint32_t w = 0; w < 16; ++w) {
-        if (w < (threadIdx.x >> 6)) run += wtot[w];
-        all += wtot[w];
-    }
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t v = a[i];
-        a[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total = all;
-}
-
 struct ViewArgs {
     const uint32_t* planes; uint64_t stride;   // the set (16-B aligned planes: stride % kTile == 0)
     const uint32_t* bits;                      // kViewWords mask words per tile, zero past n
-    const uint32_t* toff;                      // exclusive tile offsets (k_view_scan)
+    const uint32_t* toff;                      // exclusive tile offsets (V2)
     uint32_t* out; uint64_t out_stride;        // view planes
     uint32_t* map;                             // view -> set index
     uint32_t* w0s; uint32_t shift;             // nullable: view word 0 << shift | word 1 >> (32 - shift)
@@ -116,17 +72,12 @@ __global__ __launch_bounds__(kViewThreads) void k_view_compact(const ViewArgs a)
     __shared__ uint32_t wpre[kViewWords + 1];
     __shared__ uint32_t wtot0;
     __shared__ uint32_t stage[2][kTile];
-    const uint32_t t = threadIdx.x, lane = lane_id();
+    const uint32_t t = threadIdx.x;
     const uint64_t base = (uint64_t)blockIdx.x * kTile;
     if (t < kViewWords) {   // waves 0 and 1: the tile's mask words and their exclusive popcount prefix
         const uint32_t w = a.bits[(uint64_t)blockIdx.x * kViewWords + t];
         const uint32_t pc = __popc(w);
-        uint32_t inc = pc;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t x = __shfl_up(inc, o);
-            if (lane >= (uint32_t)o) inc += x;
-        }
+        const uint32_t inc = wave_scan_incl(pc);   // (waves 0 and 1 are whole: kViewWords = 128)
         wbits[t] = w;
         wpre[t] = inc - pc;   // (wave 1: + wave 0's total, below)
         if (t == 63) wtot0 = inc;
@@ -241,20 +192,13 @@ hipError_t launch_view_trim(uint32_t* bits, uint64_t n, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_view_update(uint32_t* bits, const uint32_t* idx, const uint8_t* val, uint64_t m, hipStream_t s) {
-    if (!m) return hipSuccess;
-    k_view_update<<<grid_for(m), kViewThreads, 0, s>>>(bits, idx, val, m);
-    return hipGetLastError();
-}
-
 hipError_t launch_view_count(const uint32_t* bits, uint64_t stride, uint32_t* toff, unsigned long long* d_total,
                              hipStream_t s) {
     const uint32_t ntiles = (uint32_t)(stride / kTile);
     if (!ntiles) return hipMemsetAsync(d_total, 0, 8, s);
     k_view_count<<<(ntiles + kViewThreads / 64 - 1) / (kViewThreads / 64), kViewThreads, 0, s>>>(
         reinterpret_cast<const uint2*>(bits), ntiles, toff);
-    k_view_scan<<<1, 1024, 0, s>>>(toff, ntiles, d_total);
-    return hipGetLastError();
+    return launch_excl_scan(toff, toff, 1, ntiles, d_total, s);
 }
 
 hipError_t launch_view_compact(const uint32_t* planes, uint64_t stride, const uint32_t* bits, const uint32_t* toff,

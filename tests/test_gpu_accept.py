@@ -178,6 +178,32 @@ def test_update_accept(ctx, case1):
     ctx.set_accept(None)
 
 
+@pytest.mark.parametrize("m", [257, 65537])
+def test_update_accept_many(ctx, m):
+    """m distinct indices with random values in one call (more than one block of the setter, and
+    256 blocks and one thread more): the count, every id's bit -- an id is its own nearest
+    neighbour exactly when it is accepted -- and a target sample against the oracle"""
+    n = 70001
+    ids = O.gen_ids(7600, n)
+    rng = np.random.default_rng(m)
+    mask = rng.random(n) < 0.5
+    ctx.set_ids(ids)
+    ctx.set_accept(mask)
+    idx = rng.choice(n, m, replace=False).astype(np.uint32)
+    val = (rng.random(m) < 0.5).astype(np.uint8)
+    ctx.update_accept(idx, val)
+    mask[idx] = val != 0
+    assert ctx.num_accepted == int(mask.sum())
+    got, cnt = ctx.batch_topk(ids, 1)
+    assert np.array_equal(got[:, 0] == np.arange(n, dtype=np.uint32), mask) and np.all(cnt == 1)
+    tg = O.gen_ids(7601, 24)
+    want, wcnt = expected(ids, mask, tg, 8)
+    for fn in (ctx.topk, ctx.index_topk, ctx.batch_topk):
+        got, cnt = fn(tg, 8)
+        assert_rows(got, cnt, want, wcnt, f"m={m}")
+    ctx.set_accept(None)
+
+
 # ---- 5. lifecycle ---------------------------------------------------------------------------
 def test_lifecycle(ctx, case1):
     ids, tgs, masks = case1

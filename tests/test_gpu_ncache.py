@@ -304,6 +304,30 @@ def test_update_accept_is_stream_ordered(ctx, keysets):
     assert_rows(oh.cpu().numpy().view(np.uint32), oc.cpu().numpy().view(np.uint32), want, wcnt, "after update")
 
 
+@pytest.mark.parametrize("m", [257, 65537])
+def test_update_accept_many(ctx, keysets, m):
+    """m distinct handles with random values in one call over 70,000 keys (more than one block of
+    the setter, and 256 blocks and one thread more): every key as a target at count 1 reads its own
+    bit first, against the model"""
+    keys = keysets[70000]
+    rng = np.random.default_rng(m)
+    model = NC.Model()
+    model.set(keys)
+    ctx.nc_set(keys)
+    by_handle = (rng.random(70000) < 0.5).astype(np.uint8)
+    model.set_accept(by_handle)
+    ctx.nc_set_accept(by_handle)
+    hs = rng.choice(70000, m, replace=False).astype(np.uint32)
+    val = rng.choice([0, 1, 2, 255], m).astype(np.uint8)   # any nonzero byte accepts
+    model.update_accept(hs, val)
+    ctx.nc_update_accept(hs, val)
+    want, wcnt = model.expected(keys, 1)
+    got, cnt = ctx.nc_nodes(keys, 1)
+    assert_rows(got, cnt, want, wcnt, m)
+    by_handle[hs] = val != 0
+    assert np.array_equal(got[:, 0] == np.arange(70000, dtype=np.uint32), by_handle != 0)
+
+
 def test_handle_bound_and_mask_growth(ctx, keysets):
     import opendht_amd
     keys = keysets[65]

@@ -91,6 +91,26 @@ def test_life_cycle(ctx, scripts):
     run_exact(ctx, scripts["lifecycle"], "lifecycle")
 
 
+@pytest.mark.parametrize("m", [257, 65537])
+def test_update_state_many(ctx, m):
+    """m distinct handles with random state bytes in one call (more than one block of the setter,
+    and 256 blocks and one thread more), every one of them listed in a search: the status words read
+    bit0 of each, and one more insertion per search acts on bit1"""
+    nslots, per = (m + 13) // 14 + 3, 14
+    rng = np.random.default_rng(m)
+    ids = O.gen_ids(880, nslots * (per + 1))
+    handles = (rng.permutation(nslots * (per + 1)) + 7).astype(np.uint32)
+    slots = np.arange(nslots, dtype=np.uint32)
+    first = nslots * per
+    upd = rng.choice(handles[:first], m, replace=False)
+    val = rng.choice([0, 1, 2, 3], m).astype(np.uint8)
+    script = [("reset", nslots), ("open", slots, O.gen_ids(881, nslots)),
+              ("insert", slots, RS.csr(np.full(nslots, per)), handles[:first], ids[:first]),
+              ("update_state", upd, val),
+              ("insert", slots, RS.csr(np.full(nslots, 1)), handles[first:], ids[first:])]
+    run_exact(ctx, script, f"update_state m={m}")
+
+
 def _dev(a, dtype):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a).view(dtype)).to(torch.device("cuda", 0))

@@ -263,6 +263,28 @@ def test_update_good_then_query(ctx, grown):
     assert np.all(ctx.rt_find_closest(tg, 8)[1] == 0)
 
 
+@pytest.mark.parametrize("m", [257, 65537])
+def test_update_good_many(ctx, m):
+    """m distinct nodes with random values in one call, on a table of 66,000 nodes in 256 buckets
+    (more than one block of the setter, and 256 blocks and one thread more): every node's byte -- a
+    node is the closest good node to its own id exactly when it is good -- against the oracle"""
+    ids = RC.sorted_ids(4300, 66000)
+    nn = ids.shape[0]
+    firsts, off = RC.cut(ids, RC.sizes_for(256, nn, 11))
+    rng = np.random.default_rng(m)
+    good = RC.good_mask(nn, 0.5, m)
+    ctx.rt_set(np.zeros(20, np.uint8), firsts, off, ids)
+    ctx.rt_set_good(good)
+    idx = rng.choice(nn, m, replace=False).astype(np.uint32)
+    val = rng.choice([0, 1, 2, 255], m).astype(np.uint8)   # any nonzero byte is good
+    ctx.rt_update_good(idx, val)
+    good[idx] = val != 0
+    want, wcnt = O.find_closest_batch(firsts, off, ids, good, ids, 1, threads=16)
+    got, cnt = ctx.rt_find_closest(ids, 1)
+    assert_rows(got, cnt, want, wcnt, m)
+    assert np.array_equal(got[:, 0] == np.arange(nn, dtype=np.uint32), good != 0)
+
+
 def test_version_skips_and_reuploads(ctx, grown):
     myid, firsts, off, nodes, tg = grown[False]
     nn = nodes.shape[0]

@@ -176,20 +176,35 @@ VGPR_CAPS = {
     "k_ncE": 64,              # 33  the lookup
     "k_nc_rankILb0E": 64,     # 20  insert
     "k_nc_rankILb1E": 64,     # 20  erase
-    "k_nc_scanE": 64,         # 33
     "k_nc_compactE": 64,      # 14
     "k_nc_mergeILb0E": 64,    # 16  insert
     "k_nc_mergeILb1E": 64,    # 11  erase
     "k_nc_handlesE": 64,      # 6
-    "k_nc_bits_setE": 64,     # 5
     "k_nc_bits_packE": 64,    # 15
+}
+# the shared primitives' kernels (prims.hip), which took over the scan of the block counts and the
+# indexed setters of the nc, rt and sr families under the same cap
+PRIMS_VGPR_CAPS = {
+    "k_scan_rowsIjE": 64,     # 12  u32 totals
+    "k_scan_rowsIyE": 64,     # 12  u64 totals
+    "k_bits_updateE": 64,     # 9
+    "k_bytes_updateE": 64,    # 8
 }
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_ncache_kernels_no_scratch_and_vgpr_budget():
+    check_unit_budget("ncache.hip", VGPR_CAPS)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_prims_kernels_no_scratch_and_vgpr_budget():
+    check_unit_budget("prims.hip", PRIMS_VGPR_CAPS)
+
+
+def check_unit_budget(unit, caps):
     out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-c",
-                          os.path.join(CSRC, "ncache.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
+                          os.path.join(CSRC, unit), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
                          capture_output=True, text=True, cwd=CSRC, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     kern, usage = None, {}
@@ -207,8 +222,8 @@ def test_ncache_kernels_no_scratch_and_vgpr_budget():
     assert not spills, f"kernels using scratch: {spills}"
     seen = set()
     for k, v in usage.items():
-        frags = [f for f in VGPR_CAPS if re.search(rf"\d{f}", k)]
-        assert len(frags) == 1, f"{k}: a kernel of ncache.hip without a cap"
+        frags = [f for f in caps if re.search(rf"\d{f}", k)]
+        assert len(frags) == 1, f"{k}: a kernel of {unit} without a cap"
         seen.add(frags[0])
-        assert v["VGPRs"] <= VGPR_CAPS[frags[0]], f"{k}: {v['VGPRs']} VGPRs > {VGPR_CAPS[frags[0]]}"
-    assert seen == set(VGPR_CAPS), f"kernels not found: {set(VGPR_CAPS) - seen}"
+        assert v["VGPRs"] <= caps[frags[0]], f"{k}: {v['VGPRs']} VGPRs > {caps[frags[0]]}"
+    assert seen == set(caps), f"kernels not found: {set(caps) - seen}"

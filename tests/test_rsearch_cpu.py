@@ -193,8 +193,7 @@ VGPR_CAPS = {
     "k_sr_candidateE": 64,    # 5
     "k_sr_statusE": 64,       # 6
     "k_sr_listsE": 64,        # 6
-    "k_sr_state_setE": 64,    # 3
-}
+}   # (update_state's byte setter: prims.hip, capped in test_ncache_cpu.py)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")

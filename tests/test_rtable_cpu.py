@@ -132,8 +132,7 @@ VGPR_CAPS = {
     "k_rtILi2ELj16E": 64,    # 17  closer, K = 16
     "k_rtILi2ELj32E": 64,    # 20  closer, K = 32
     "k_rt_gpreE": 64,        # 42
-    "k_rt_good_setE": 64,    # 3
-}
+}   # (update_good's byte setter: prims.hip, capped in test_ncache_cpu.py)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
