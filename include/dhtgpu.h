@@ -47,6 +47,19 @@
  * to a context must outlive it: a later call that moves a workspace slot to another stream
  * records an event on the slot's previous stream, and dhtgpu_ctx_destroy synchronises the
  * streams the slots last used.
+ *
+ * Host arrays: every host array passed to an entry point -- those of the setters that do not
+ * synchronise included (dhtgpu_update_accept, dhtgpu_rt_update_good / _set_good,
+ * dhtgpu_nc_update_accept / _set_accept, dhtgpu_sr_update_state / _set_state / _open / _expire /
+ * _set_candidate) -- is the caller's again when the call returns, PROVIDED it lies in ordinary
+ * (pageable) host memory: stack, heap, std::vector.  The library reads such an array with
+ * hipMemcpyAsync into its own staging on the context's stream, and HIP performs that copy
+ * synchronously with respect to the host when the host side is not pinned; the kernels then read
+ * the staging, never the caller's memory, and back-to-back setters reuse one staging buffer in
+ * stream order (a growth of it frees the old one only after the device has drained).  An array in
+ * pinned memory (hipHostMalloc, hipHostRegister) is read stream-ordered instead: it must stay
+ * unchanged until the context's stream has passed the call, i.e. until any synchronising call of
+ * the context or a hipStreamSynchronize(dhtgpu_ctx_stream(ctx)) has returned.
  */
 #ifndef DHTGPU_H
 #define DHTGPU_H
