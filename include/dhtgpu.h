@@ -383,6 +383,75 @@ int dhtgpu_rt_closer_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_s
 int dhtgpu_rt_closer(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, uint32_t count, uint32_t min_nodes,
                      uint8_t* out_flag, uint32_t* out_cnt);
 
+/* ---- K1g: growing the resident table ---------------------------------------------------------- */
+/* RoutingTable::onNewNode (src/routing_table.cpp:204-262, split :87-107 / :176-202) and
+ * Dht::expireBuckets (src/dht.cpp:179-192) applied to the resident table on the device, so that a
+ * caller without a host table can build one, and one with a host table need not re-pack and
+ * upload it for every node that enters a bucket.  All K1w queries go on answering from the result.
+ *
+ * A node is (id, handle, state byte, tail).  "The same node" is the same handle.  State byte:
+ * bit 0 Node::isGood(now), bit 1 isExpired(), bit 2 isPendingMessage(); an expired node is never
+ * good (not checked).
+ *
+ * Handles.  dhtgpu_rt_set is unchanged: a node it uploads has handle = its upload position and
+ * state = good.  The first rtg mutation (on_new_node with m > 0, expire, set_state, update_state)
+ * turns the table into its grown form.  From then on the out_idx of dhtgpu_rt_find_closest[_dev]
+ * and dhtgpu_rt_reply[_dev] are HANDLES -- on a table that never grew these equal the positions, so
+ * existing callers see no difference -- and so are the idx of dhtgpu_rt_update_good (idx >=
+ * DHTGPU_RTG_MAX_HANDLE: DHTGPU_EINVAL).  dhtgpu_rt_set_good, a positional array, returns
+ * DHTGPU_EINVAL on a grown table: dhtgpu_rtg_set_state replaces it.  The next dhtgpu_rt_set drops
+ * the grown form, also when its version equals an earlier upload's.
+ * A new node's handle (< DHTGPU_RTG_MAX_HANDLE) must differ from every resident handle of another
+ * node, and ids are distinct per handle.  The same handle twice in one batch is legal: the second
+ * is KNOWN if the first was placed into that bucket.  Handles that are not resident are ignored by
+ * the state setters.
+ *
+ * Limits.  Every bucket of the resident table must hold at most 8 nodes, else DHTGPU_EINVAL (known
+ * from bucket_off at dhtgpu_rt_set time; only crafted uploads exceed it, onNewNode never does).
+ * nb <= 256 and nn <= 2,048 hold throughout.  An insertion whose split would need a 257th bucket
+ * gets DHTGPU_RTG_UNAPPLIED, and so does every insertion after it; the insertions before it stay
+ * applied and the call returns DHTGPU_ERANGE.  A table grown by onNewNode from one bucket cannot
+ * get there (at most 161 buckets, about 224 in client mode).  A bucket at depth 160 cannot split:
+ * the node is FULL.
+ *
+ * Errors.  DHTGPU_ENOIDS before the first dhtgpu_rt_set.  A handle at or past the bound, or a
+ * missing tail array on a table set with tails, gives DHTGPU_EINVAL with nothing applied. */
+#define DHTGPU_RTG_NONE 0        /* no bucket (empty table) */
+#define DHTGPU_RTG_KNOWN 1       /* handle already in the bucket */
+#define DHTGPU_RTG_PLACED 2      /* inserted at the bucket's front */
+#define DHTGPU_RTG_REPLACED 3    /* overwrote the first expired node (list order); aux = its handle */
+#define DHTGPU_RTG_FULL 4        /* bucket full, node not inserted (the caller may cache it); aux = the ping pick */
+#define DHTGPU_RTG_UNAPPLIED 5   /* past a limit, nothing done */
+#define DHTGPU_RTG_MAX_HANDLE 65536u
+/* flags bit0: RoutingTable::is_client.  ids20[m*20], handles[m], state[m] (nullable: every new node
+ * good), node_tail[m*(alen+2)] (required iff the table was set with tails).  Applied in batch
+ * order.  out_res[m] = DHTGPU_RTG_*; out_aux[m] (nullable) = the evicted handle (REPLACED), the
+ * ping pick of a FULL bucket -- its first node in list order that is not good and has no pending
+ * message; the library sends nothing -- or DHTGPU_NONE; out_stat[3] (nullable) = nb, nn and the
+ * splits since the upload, after the call.  m == 0 is DHTGPU_OK and changes nothing.  Synchronous,
+ * like dhtgpu_nc_insert; not to be called while rt calls are in flight (calls already issued on
+ * other streams keep reading the table as it was: it is written to the other blob of a pair). */
+int dhtgpu_rtg_on_new_node(dhtgpu_ctx* ctx, const uint8_t* ids20, const uint32_t* handles, const uint8_t* state,
+                           const uint8_t* node_tail, uint32_t m, uint32_t flags, uint8_t* out_res, uint32_t* out_aux,
+                           uint32_t* out_stat);
+/* Dht::expireBuckets: every node whose state says expired leaves its bucket; the survivors keep
+ * their order and the buckets stay.  out_handles (nullable; room for the nn before the call)
+ * receives the removed handles in no particular order, *out_removed (nullable) their number.
+ * Synchronous. */
+int dhtgpu_rtg_expire(dhtgpu_ctx* ctx, uint32_t* out_handles, uint32_t* out_removed);
+/* The state bytes: set_state gives every resident node with handle < nh the byte
+ * state_by_handle[handle] (nh <= DHTGPU_RTG_MAX_HANDLE); update_state sets m of them (distinct
+ * handles).  Stream-ordered on the context's stream like dhtgpu_rt_update_good, once the table is
+ * in its grown form (the call that turns it synchronises). */
+int dhtgpu_rtg_set_state(dhtgpu_ctx* ctx, const uint8_t* state_by_handle, uint32_t nh);
+int dhtgpu_rtg_update_state(dhtgpu_ctx* ctx, const uint32_t* handles, const uint8_t* val, uint32_t m);
+int dhtgpu_rtg_size(dhtgpu_ctx* ctx, uint32_t* out_nb, uint32_t* out_nn);
+/* The resident table back on the host, each array nullable: firsts20[nb*20], bucket_off[nb+1],
+ * and per node in bucket list order and in-bucket list order ids20[nn*20], handles[nn], state[nn]
+ * -- the arguments of a dhtgpu_rt_set that would upload the same table.  Synchronous. */
+int dhtgpu_rtg_export(dhtgpu_ctx* ctx, uint8_t* firsts20, uint32_t* bucket_off, uint8_t* ids20, uint32_t* handles,
+                      uint8_t* state);
+
 /* ---- K8w: the resident NodeCache ------------------------------------------------------------- */
 /* NodeCache::NodeMap (include/opendht/node_cache.h:43: std::map<InfoHash, weak_ptr<Node>>) kept on
  * the device between calls and changed incrementally, so that a key heard of or dropped costs one

@@ -121,6 +121,18 @@ inline void put_tail(std::vector<uint8_t>& out, const NodeT& nd, bool af_inet6) 
     out.insert(out.end(), p, p + 2);
 }
 
+/* A node's state byte for dhtgpu_rtg_*: bit 0 isGood(now), bit 1 isExpired(), bit 2
+ * isPendingMessage().  A node type without the last two (a snapshot-only caller's) gives bit 0. */
+template <class NodeT, class TimePoint>
+inline auto node_state(const NodeT& n, TimePoint now, int)
+    -> decltype((void)n.isExpired(), (void)n.isPendingMessage(), uint8_t()) {
+    return (uint8_t)((n.isGood(now) ? 1 : 0) | (n.isExpired() ? 2 : 0) | (n.isPendingMessage() ? 4 : 0));
+}
+template <class NodeT, class TimePoint>
+inline uint8_t node_state(const NodeT& n, TimePoint now, long) {
+    return n.isGood(now) ? 1 : 0;
+}
+
 /* InfoHash::xorCmp(a, b) < 0 for target t (include/opendht/infohash.h:179-194): at the first
  * byte where a and b differ, the one whose byte XOR t's is smaller is closer. */
 inline bool xor_closer(const uint8_t* t, const uint8_t* a, const uint8_t* b) {
@@ -419,8 +431,19 @@ private:
  *                                split): the snapshot rule of TableSnapshot plus every node's
  *                                address || port (af 4 / 6; 0 = no tails, no replies); a version
  *                                != 0 equal to the last one's skips the upload
- *   refresh(table, now)          once per batch: the isGood(now) bits only
+ *   refresh(table, now)          once per batch: the isGood(now) bits only (by handle, with the
+ *                                expired and pending bits, once the mirror has grown)
  *   findClosestNodesBatch / replyNodesBatch / closerThanSelfBatch   the batch itself
+ * Between two assigns the mirror follows the table node by node (dhtgpu_rtg_*):
+ *   noteNewNode(node, now)       after the caller's own table.onNewNode(node, ...): queues the
+ *                                node's id, handle (its slot in the handle -> NodePtr table), state
+ *                                byte and tail
+ *   noteExpire()                 after Dht::expireBuckets: queues the sweep
+ *   flush(table)                 the queue, one device call per run of new nodes or sweep, in order;
+ *                                every device path below flushes first.  Evicted and expired handles
+ *                                go to a free list.  A queue longer than max_flush_nodes, an
+ *                                UNAPPLIED result or a device error falls back to assign(table).
+ *   onNewNodeBatch(...)          stand-alone use, no host table: one call, the result codes
  * Batches below min_device_batch (replies: min_reply_batch) targets never touch the device: they
  * run the reference's walk on the table they are given (detail::find_closest_host) and, for replies, pack the records on
  * the host -- neither assign nor refresh is needed for them.  Larger batches answer from the
@@ -433,6 +456,12 @@ private:
  * flags were not measured and follow the node lists' threshold. */
 static const size_t kMinResidentBatch = 768;
 static const size_t kMinResidentReplyBatch = 320;
+/* Most queued nodes ResidentTable::flush sends node by node; a longer queue re-assigns the table.
+ * From the measured crossover of DESIGN.md §5m (tools/rtgrow_bench.py): a flush costs 39.5 us + 1.19
+ * us per node (cfg-1 table; the client table 43.2 + 1.35), the upload of the re-packed table 77.2 us
+ * (87.2) whatever the batch: (77.2 - 39.5) / 1.19 = 31.9 nodes (32.5).  The host's re-pack is on
+ * top of the upload and was not timed, so the threshold errs towards assign. */
+static const size_t kMaxResidentFlush = 32;
 
 template <class Table, class TimePoint>
 class ResidentTable {
@@ -440,28 +469,39 @@ public:
     typedef typename TableSnapshot<Table, TimePoint>::NodePtr NodePtr;
     template <class HashT>
     ResidentTable(Context& ctx, const HashT& myid)
-        : min_device_batch(kMinResidentBatch), min_reply_batch(kMinResidentReplyBatch), ctx_(ctx), alen_(0) {
+        : min_device_batch(kMinResidentBatch), min_reply_batch(kMinResidentReplyBatch),
+          max_flush_nodes(kMaxResidentFlush), is_client(false), ctx_(ctx), alen_(0), af_(0), grown_(false),
+          have_now_(false), now_() {
         std::memcpy(myid_, myid.data(), DHTGPU_HASH_LEN);
     }
     size_t min_device_batch;   // smallest batch answered from the mirror: node lists and closeness flags
     size_t min_reply_batch;    // ... replies
+    size_t max_flush_nodes;    // most queued nodes flush() sends node by node; more: assign
+    bool is_client;            // RoutingTable::is_client, for the device's split rule
 
     void assign(const Table& table, unsigned af, uint64_t version = 0) {
         if (af != 0 && af != 4 && af != 6) throw Error(DHTGPU_EINVAL, "ResidentTable::assign: af");
         alen_ = af == 4 ? 4u : af == 6 ? 16u : 0u;
+        af_ = af;
         std::vector<uint8_t> firsts, ids, tail;
         std::vector<uint32_t> off;
         nodes_.clear();
+        free_.clear();
+        slot_of_.clear();
+        queue_.clear();   // what was queued is in the table that is uploaded now
+        grown_ = false;
         for (const auto& b : table) {
             detail::put_id(firsts, b.first);
             off.push_back((uint32_t)nodes_.size());
             for (const auto& n : b.nodes) {
                 detail::put_id(ids, n->id);
                 if (alen_) detail::put_tail(tail, *n, af == 6);
+                slot_of_[n.get()] = (uint32_t)nodes_.size();
                 nodes_.push_back(n);
             }
         }
         off.push_back((uint32_t)nodes_.size());
+        resident_.assign(nodes_.size(), 1);   // what is uploaded is resident
         static const uint8_t none[DHTGPU_HASH_LEN] = {0};
         check(dhtgpu_rt_set(ctx_.get(), myid_, (uint32_t)(off.size() - 1), firsts.data(), off.data(),
                             ids.empty() ? nullptr : ids.data(), alen_ ? (tail.empty() ? none : tail.data()) : nullptr,
@@ -469,8 +509,16 @@ public:
               "rt_set");
     }
 
-    /* the isGood(now) bits of the assigned nodes, in the assigned order */
+    /* the isGood(now) bits of the assigned nodes, in the assigned order; on a grown mirror the state
+     * bytes of the resident nodes by handle */
     void refresh(const Table& table, TimePoint now) {
+        now_ = now;
+        have_now_ = true;
+        flush(table);
+        if (grown_) {
+            check(send_states(now), "rtg_set_state");
+            return;
+        }
         std::vector<uint8_t> good;
         good.reserve(nodes_.size());
         for (const auto& b : table)
@@ -481,13 +529,14 @@ public:
 
     template <class HashT>
     std::vector<std::vector<NodePtr>> findClosestNodesBatch(const Table& table, const HashT* targets, size_t q,
-                                                            TimePoint now, size_t count) const {
+                                                            TimePoint now, size_t count) {
         std::vector<std::vector<NodePtr>> res(q);
         if (q == 0 || count == 0) return res;
         if (host(q, count)) {
             for (size_t i = 0; i < q; ++i) detail::find_closest_host(table, targets[i], now, count, res[i]);
             return res;
         }
+        flush(table);
         const std::vector<uint8_t> t = pack(targets, q);
         std::vector<uint32_t> idx(q * count), cnt(q);
         check(dhtgpu_rt_find_closest(ctx_.get(), t.data(), (uint32_t)q, (uint32_t)count, idx.data(), cnt.data()),
@@ -502,7 +551,7 @@ public:
     /* the find_node / get reply per target: findClosestNodes(target, now, 8) as bufferNodes packs it */
     template <class HashT>
     std::vector<std::vector<uint8_t>> replyNodesBatch(const Table& table, const HashT* targets, size_t q,
-                                                      TimePoint now) const {
+                                                      TimePoint now) {
         if (!alen_) throw Error(DHTGPU_EINVAL, "ResidentTable::replyNodesBatch: assigned without an address family");
         const uint32_t rec = 20 + alen_ + 2;
         std::vector<std::vector<uint8_t>> res(q);
@@ -511,6 +560,7 @@ public:
             for (size_t i = 0; i < q; ++i) res[i] = detail::reply_nodes_host(table, targets[i], now, alen_ == 16);
             return res;
         }
+        flush(table);
         const std::vector<uint8_t> t = pack(targets, q);
         std::vector<uint8_t> out(q * 8 * rec);
         std::vector<uint32_t> len(q);
@@ -524,7 +574,7 @@ public:
      * onAnnounce's */
     template <class HashT>
     std::vector<uint8_t> closerThanSelfBatch(const Table& table, const HashT* targets, size_t q, TimePoint now,
-                                             size_t count, size_t min_nodes) const {
+                                             size_t count, size_t min_nodes) {
         std::vector<uint8_t> flag(q, 0);
         if (q == 0 || count == 0) return flag;
         if (host(q, count)) {
@@ -532,6 +582,7 @@ public:
                 flag[i] = detail::closer_than_self_host(table, targets[i], now, count, min_nodes, myid_);
             return flag;
         }
+        flush(table);
         const std::vector<uint8_t> t = pack(targets, q);
         check(dhtgpu_rt_closer(ctx_.get(), t.data(), (uint32_t)q, (uint32_t)count, (uint32_t)min_nodes, flag.data(),
                                nullptr),
@@ -539,7 +590,147 @@ public:
         return flag;
     }
 
+    /* ---- the mirror follows the table (dhtgpu_rtg_*) ---- */
+    void noteNewNode(const NodePtr& node, TimePoint now) {
+        Op op;
+        op.expire = false;
+        std::memcpy(op.id, node->id.data(), DHTGPU_HASH_LEN);
+        op.handle = slot(node);
+        op.state = detail::node_state(*node, now, 0);
+        now_ = now;
+        have_now_ = true;
+        std::vector<uint8_t> t;
+        if (alen_) detail::put_tail(t, *node, alen_ == 16);
+        std::memset(op.tail, 0, sizeof op.tail);
+        if (!t.empty()) std::memcpy(op.tail, t.data(), t.size());
+        queue_.push_back(op);
+    }
+    void noteExpire() {
+        Op op = Op();
+        op.expire = true;
+        queue_.push_back(op);
+    }
+    size_t queued() const { return queue_.size(); }
+    /* the handle -> node table: what a result index of the mirror names (null: a free handle) */
+    const std::vector<NodePtr>& handles() const { return nodes_; }
+
+    void flush(const Table& table) {
+        if (queue_.empty()) return;
+        size_t news = 0;
+        for (const Op& op : queue_) news += op.expire ? 0 : 1;
+        bool ok = news <= max_flush_nodes;
+        // an uploaded mirror knows its nodes' good bits only: onNewNode and the sweep read the
+        // expired and pending bits too, so the first mutation is preceded by the states by handle
+        if (ok && !grown_) ok = have_now_ && send_states(now_) == DHTGPU_OK;
+        for (size_t b = 0; ok && b < queue_.size();) {
+            if (queue_[b].expire) {
+                ok = flush_expire();
+                ++b;
+                continue;
+            }
+            size_t e = b;
+            while (e < queue_.size() && !queue_[e].expire) ++e;
+            ok = flush_new(b, e);
+            b = e;
+        }
+        queue_.clear();
+        if (!ok) assign(table, af_);
+    }
+
+    /* Stand-alone use: m nodes given as ids, caller-owned handles (< DHTGPU_RTG_MAX_HANDLE), state
+     * bytes (nullable: good) and tails (alen + 2 bytes each, iff assigned with an address family), applied
+     * in order to the mirror as last assigned; returns the DHTGPU_RTG_* codes, aux (nullable) the
+     * evicted handles / ping picks.  DHTGPU_ERANGE (a 257th bucket) does not throw: the codes say
+     * UNAPPLIED from there on. */
+    template <class HashT>
+    std::vector<uint8_t> onNewNodeBatch(const HashT* ids, const uint32_t* handles, const uint8_t* state,
+                                        const uint8_t* tails, size_t m, std::vector<uint32_t>* aux = nullptr) {
+        std::vector<uint8_t> res(m, 0);
+        if (!m) return res;
+        const std::vector<uint8_t> x = pack(ids, m);
+        std::vector<uint32_t> a(m, DHTGPU_NONE);
+        const int r = dhtgpu_rtg_on_new_node(ctx_.get(), x.data(), handles, state, tails, (uint32_t)m, is_client ? 1u : 0u,
+                                             res.data(), a.data(), nullptr);
+        if (r != DHTGPU_ERANGE) check(r, "rtg_on_new_node");
+        grown_ = true;
+        if (aux) aux->swap(a);
+        return res;
+    }
+
 private:
+    struct Op {
+        bool expire;
+        uint8_t id[DHTGPU_HASH_LEN];
+        uint32_t handle;
+        uint8_t state;
+        uint8_t tail[18];
+    };
+    /* the node's handle: the one it holds, else a free one, else a new one */
+    uint32_t slot(const NodePtr& node) {
+        const auto it = slot_of_.find(node.get());
+        if (it != slot_of_.end()) return it->second;
+        uint32_t h;
+        if (!free_.empty()) {
+            h = free_.back();
+            free_.pop_back();
+            nodes_[h] = node;
+        } else {
+            h = (uint32_t)nodes_.size();
+            nodes_.push_back(node);
+        }
+        slot_of_[node.get()] = h;
+        if (h >= resident_.size()) resident_.resize(h + 1, 0);
+        resident_[h] = 0;
+        return h;
+    }
+    void release(uint32_t h) {
+        if (h >= nodes_.size() || !nodes_[h]) return;
+        slot_of_.erase(nodes_[h].get());
+        nodes_[h] = NodePtr();
+        if (h < resident_.size()) resident_[h] = 0;
+        free_.push_back(h);
+    }
+    /* one state byte per handle, as of `now` (turns an uploaded mirror into its grown form) */
+    int send_states(TimePoint now) {
+        std::vector<uint8_t> st(nodes_.size(), 0);
+        for (size_t h = 0; h < nodes_.size(); ++h)
+            if (nodes_[h]) st[h] = detail::node_state(*nodes_[h], now, 0);
+        const int r = dhtgpu_rtg_set_state(ctx_.get(), st.empty() ? nullptr : st.data(), (uint32_t)st.size());
+        if (r == DHTGPU_OK) grown_ = true;
+        return r;
+    }
+    bool flush_new(size_t b, size_t e) {
+        const size_t m = e - b, rec = alen_ ? alen_ + 2 : 0;
+        std::vector<uint8_t> ids, st(m), tails, res(m);
+        std::vector<uint32_t> h(m), aux(m);
+        for (size_t i = b; i < e; ++i) {
+            if (queue_[i].handle >= DHTGPU_RTG_MAX_HANDLE) return false;
+            ids.insert(ids.end(), queue_[i].id, queue_[i].id + DHTGPU_HASH_LEN);
+            tails.insert(tails.end(), queue_[i].tail, queue_[i].tail + rec);
+            h[i - b] = queue_[i].handle;
+            st[i - b] = queue_[i].state;
+        }
+        grown_ = true;
+        if (dhtgpu_rtg_on_new_node(ctx_.get(), ids.data(), h.data(), st.data(), rec ? tails.data() : nullptr, (uint32_t)m,
+                                   is_client ? 1u : 0u, res.data(), aux.data(), nullptr) != DHTGPU_OK)
+            return false;
+        for (size_t i = 0; i < m; ++i) {
+            if (res[i] == DHTGPU_RTG_UNAPPLIED) return false;
+            if (res[i] == DHTGPU_RTG_REPLACED) release(aux[i]);
+            if (res[i] == DHTGPU_RTG_PLACED || res[i] == DHTGPU_RTG_REPLACED) resident_[h[i]] = 1;
+        }
+        for (size_t i = 0; i < m; ++i)   // a node the table did not take keeps no handle
+            if (!resident_[h[i]]) release(h[i]);
+        return true;
+    }
+    bool flush_expire() {
+        grown_ = true;
+        std::vector<uint32_t> gone(nodes_.size() + 1);
+        uint32_t n = 0;
+        if (dhtgpu_rtg_expire(ctx_.get(), gone.data(), &n) != DHTGPU_OK) return false;
+        for (uint32_t i = 0; i < n; ++i) release(gone[i]);
+        return true;
+    }
     bool host(size_t q, size_t count) const { return q < min_device_batch || count > DHTGPU_MAX_K; }
     template <class HashT>
     static std::vector<uint8_t> pack(const HashT* targets, size_t q) {
@@ -551,7 +742,15 @@ private:
     Context& ctx_;
     uint8_t myid_[DHTGPU_HASH_LEN];
     uint32_t alen_;
-    std::vector<NodePtr> nodes_;
+    unsigned af_;
+    bool grown_;                               // the mirror took a dhtgpu_rtg_* mutation since the last assign
+    bool have_now_;                            // now_ holds the time of the last note or refresh
+    TimePoint now_;
+    std::vector<NodePtr> nodes_;               // handle -> node (after assign: the upload position)
+    std::vector<uint8_t> resident_;            // handle -> the mirror holds it
+    std::vector<uint32_t> free_;               // handles of evicted and expired nodes
+    std::map<const void*, uint32_t> slot_of_;  // node -> its handle
+    std::vector<Op> queue_;
 };
 
 /* NodeCache's map resident on the device (dhtgpu_nc_*): the initiator path.  The adapter owns the

@@ -32,6 +32,9 @@ LIB_PATH = os.environ.get("DHTGPU_LIB") or os.path.join(os.path.dirname(os.path.
 NONE = 0xFFFFFFFF
 MAX_K = 32
 SR_CAP = 64   # DHTGPU_SR_CAP: entries per resident search row
+# DHTGPU_RTG_*: the results of rtg_on_new_node
+RTG_NONE, RTG_KNOWN, RTG_PLACED, RTG_REPLACED, RTG_FULL, RTG_UNAPPLIED = range(6)
+RTG_MAX_HANDLE = 65536
 # status codes (include/dhtgpu.h)
 EINVAL, ENOMEM, EDEVICE, ENOIDS, EUNSORTED, ERANGE = -1, -2, -3, -4, -5, -6
 
@@ -156,6 +159,13 @@ def lib():
                                   _vp, _vp], ctypes.c_int),
         "dhtgpu_rt_closer": ([_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u32p],
                              ctypes.c_int),
+        "dhtgpu_rtg_on_new_node": ([_vp, _u8p, _u32p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u32p, _u32p],
+                                   ctypes.c_int),
+        "dhtgpu_rtg_expire": ([_vp, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_rtg_set_state": ([_vp, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_rtg_update_state": ([_vp, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_rtg_size": ([_vp, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_rtg_export": ([_vp, _u8p, _u32p, _u8p, _u32p, _u8p], ctypes.c_int),
         "dhtgpu_nc_set": ([_vp, _u8p, _u32p, ctypes.c_uint64], ctypes.c_int),
         "dhtgpu_nc_insert": ([_vp, _u8p, _u32p, _u8p, ctypes.c_uint32, _u8p], ctypes.c_int),
         "dhtgpu_nc_erase": ([_vp, _u8p, ctypes.c_uint32, _u8p], ctypes.c_int),
@@ -210,7 +220,8 @@ def exported_symbols():
             "dhtgpu_update_accept", "dhtgpu_num_accepted", "dhtgpu_write_ids", "dhtgpu_batch_plan",
             "dhtgpu_rt_set", "dhtgpu_rt_set_good", "dhtgpu_rt_update_good", "dhtgpu_rt_find_closest_dev",
             "dhtgpu_rt_find_closest", "dhtgpu_rt_reply_dev", "dhtgpu_rt_reply", "dhtgpu_rt_closer_dev",
-            "dhtgpu_rt_closer", "dhtgpu_nc_set", "dhtgpu_nc_insert", "dhtgpu_nc_erase", "dhtgpu_nc_update_accept",
+            "dhtgpu_rt_closer", "dhtgpu_rtg_on_new_node", "dhtgpu_rtg_expire", "dhtgpu_rtg_set_state",
+            "dhtgpu_rtg_update_state", "dhtgpu_rtg_size", "dhtgpu_rtg_export", "dhtgpu_nc_set", "dhtgpu_nc_insert", "dhtgpu_nc_erase", "dhtgpu_nc_update_accept",
             "dhtgpu_nc_set_accept", "dhtgpu_nc_size", "dhtgpu_nc_export", "dhtgpu_nc_nodes_dev", "dhtgpu_nc_nodes",
             "dhtgpu_sr_reset", "dhtgpu_sr_open", "dhtgpu_sr_expire", "dhtgpu_sr_set_state", "dhtgpu_sr_update_state",
             "dhtgpu_sr_set_candidate", "dhtgpu_sr_insert", "dhtgpu_sr_insert_dev", "dhtgpu_sr_refill",
@@ -524,6 +535,78 @@ class Context:
     def rt_closer_dev(self, t_planes_ptr, t_stride, q, count, min_nodes, out_flag_ptr, out_cnt_ptr=None, stream=None):
         _check(lib().dhtgpu_rt_closer_dev(self._h, t_planes_ptr, t_stride, q, count, min_nodes, out_flag_ptr,
                                           out_cnt_ptr, stream), "rt_closer_dev")
+
+    # ---- K1g: growing the resident table -------------------------------------------
+    def rtg_on_new_node(self, ids, handles, state=None, node_tail=None, client=False):
+        """RoutingTable::onNewNode for m nodes, in order, on the resident table: ((m,) uint8
+        RTG_* results, (m,) uint32 aux -- evicted handle / ping pick / NONE --, (3,) uint32 nb, nn,
+        splits).  state (m,): bit 0 good, 1 expired, 2 pending (None: good).  A batch that meets
+        the 256-bucket limit raises ERANGE after applying what came before it, as sr_insert does:
+        the three arrays are then the exception's `res`, `aux` and `stat`."""
+        ids = _ids(ids) if len(ids) else np.zeros((0, 20), np.uint8)
+        m = ids.shape[0]
+        h = np.ascontiguousarray(handles, dtype=np.uint32).reshape(-1)
+        if h.shape[0] != m:
+            raise ValueError("handles must have one entry per node")
+        s = None
+        if state is not None:
+            s = np.ascontiguousarray(state, dtype=np.uint8).reshape(-1)
+            if s.shape[0] != m:
+                raise ValueError("state must have one entry per node")
+        t = None
+        if node_tail is not None:
+            t = np.ascontiguousarray(node_tail, dtype=np.uint8).reshape(m, -1)
+            if m and t.shape[1] != getattr(self, "_rt", (0, t.shape[1]))[1]:
+                raise ValueError("node_tail rows must be as long as the table's")
+        res = np.zeros(m, dtype=np.uint8)
+        aux = np.full(m, NONE, dtype=np.uint32)
+        stat = np.zeros(3, dtype=np.uint32)
+        code = lib().dhtgpu_rtg_on_new_node(self._h, _p(ids, _u8p), _p(h, _u32p), _p(s, _u8p) if s is not None else None,
+                                            _p(t, _u8p) if t is not None and m else None, m, int(bool(client)),
+                                            _p(res, _u8p), _p(aux, _u32p), _p(stat, _u32p))
+        if code != 0:
+            e = DhtGpuError(code, "rtg_on_new_node")
+            e.res, e.aux, e.stat = res, aux, stat
+            raise e
+        return res, aux, stat
+
+    def rtg_expire(self):
+        """Dht::expireBuckets on the resident table: the removed handles, (r,) uint32, in no particular order."""
+        nb, nn = self.rtg_size()
+        out = np.zeros(max(nn, 1), dtype=np.uint32)
+        r = ctypes.c_uint32(0)
+        _check(lib().dhtgpu_rtg_expire(self._h, _p(out, _u32p), ctypes.byref(r)), "rtg_expire")
+        return out[: r.value].copy()
+
+    def rtg_set_state(self, state_by_handle):
+        """State bytes by handle, (nh,) uint8, for every resident node whose handle is below nh."""
+        s = np.ascontiguousarray(state_by_handle, dtype=np.uint8).reshape(-1)
+        _check(lib().dhtgpu_rtg_set_state(self._h, _p(s, _u8p) if s.size else None, s.shape[0]), "rtg_set_state")
+
+    def rtg_update_state(self, handles, val):
+        """state[handles[j]] = val[j] (val: array or one value for all); handles not resident are ignored."""
+        h = np.ascontiguousarray(handles, dtype=np.uint32).reshape(-1)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(val), h.shape)).astype(np.uint8).reshape(-1)
+        _check(lib().dhtgpu_rtg_update_state(self._h, _p(h, _u32p), _p(v, _u8p), h.shape[0]), "rtg_update_state")
+
+    def rtg_size(self):
+        """(buckets, nodes) of the resident table."""
+        nb, nn = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib().dhtgpu_rtg_size(self._h, ctypes.byref(nb), ctypes.byref(nn)), "rtg_size")
+        return nb.value, nn.value
+
+    def rtg_export(self):
+        """The resident table: firsts (nb, 20), bucket_off (nb + 1,), ids (nn, 20), handles (nn,),
+        state (nn,) -- bucket list order, in-bucket list order."""
+        nb, nn = self.rtg_size()
+        firsts = np.zeros((nb, 20), dtype=np.uint8)
+        off = np.zeros(nb + 1, dtype=np.uint32)
+        ids = np.zeros((max(nn, 1), 20), dtype=np.uint8)
+        h = np.zeros(max(nn, 1), dtype=np.uint32)
+        st = np.zeros(max(nn, 1), dtype=np.uint8)
+        _check(lib().dhtgpu_rtg_export(self._h, _p(firsts, _u8p) if nb else None, _p(off, _u32p), _p(ids, _u8p),
+                                       _p(h, _u32p), _p(st, _u8p)), "rtg_export")
+        return firsts, off, ids[:nn], h[:nn], st[:nn]
 
     # ---- K8w: the resident NodeCache ------------------------------------------------
     def nc_set(self, ids, handles=None):

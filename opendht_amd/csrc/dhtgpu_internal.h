@@ -268,6 +268,52 @@ hipError_t launch_rt_reply(const RtView& v, const uint32_t* tp, uint64_t ts, uin
 hipError_t launch_rt_closer(const RtView& v, const uint32_t* tp, uint64_t ts, uint32_t q, uint32_t count,
                             uint32_t min_nodes, uint8_t* out_flag, uint32_t* out_cnt, hipStream_t s);
 
+// rtgrow.hip: K1g, onNewNode / split / expireBuckets on the resident table (dhtgpu_rtg_*).  A grown
+// table lives in a blob of fixed geometry -- kRtgBuckets buckets, kRtgNodes nodes (the node planes'
+// stride) -- that carries, beside K1w's arrays, each node's handle and its state byte.
+constexpr uint32_t kRtgBuckets = 256, kRtgNodes = 2048, kRtgMaxHandle = 65536;
+struct RtgBlob {
+    uint32_t* fp;        // firsts planes, fp[w * nb + b]
+    uint32_t* off;       // [kRtgBuckets + 1]
+    uint32_t* gpre;      // [kRtgBuckets + 1]
+    uint32_t* myid;      // 5 words
+    uint32_t* np;        // node planes, np[w * kRtgNodes + i]
+    uint8_t* good;       // [kRtgNodes] bit 0 of the state
+    uint8_t* state;      // [kRtgNodes] bit 0 isGood, bit 1 isExpired, bit 2 isPendingMessage
+    uint32_t* handle;    // [kRtgNodes] the caller's handle of node i
+    uint8_t* tail;       // [kRtgNodes * 18]
+};
+// a batch of new nodes (device arrays): 20-byte ids, handles, state bytes (nullable: good), tails
+// (alen + 2 bytes each; alen = the table's), results
+struct RtgBatch {
+    const uint8_t* ids20;
+    const uint32_t* handles;
+    const uint8_t* state;
+    const uint8_t* tail;
+    uint32_t m, flags, alen;
+    uint8_t* out_res;
+    uint32_t* out_aux;
+};
+// One workgroup: the table v (hsrc / ssrc: its handle and state planes, null for a table that never
+// grew: handle = position, state = good) through LDS into d; hmap[kRtgMaxHandle] = position by
+// handle (DHT_NONE: not resident; all DHT_NONE on entry for a table that never grew).  Every bucket
+// of v holds at most 8 nodes.  out_stat[4] = {nb, nn, splits, stopped at a 257th bucket} /
+// {nb, nn, 0, nodes removed}; out_handles (nullable) = the removed handles, any order.
+hipError_t launch_rtg_insert(const RtView& v, const uint32_t* hsrc, const uint8_t* ssrc, const RtgBlob& d, uint32_t* hmap,
+                             const RtgBatch& a, uint32_t* out_stat, hipStream_t s);
+hipError_t launch_rtg_expire(const RtView& v, const uint32_t* hsrc, const uint8_t* ssrc, const RtgBlob& d, uint32_t* hmap,
+                             uint32_t* out_handles, uint32_t* out_stat, hipStream_t s);
+// the state of every resident node whose handle is below nh = by_handle[handle] (device array)
+hipError_t launch_rtg_set_state(const RtgBlob& d, uint32_t nn, const uint8_t* by_handle, uint32_t nh, hipStream_t s);
+// launch_bytes_update through the handle -> position map: i = hmap[h[j]] for h[j] < kRtgMaxHandle,
+// handles that are not resident skipped.  whole: the state byte val[j] (good[i] = its bit 0);
+// else good[i] = val[j] != 0 and bit 0 of state[i] follows it.  (It stands here and not in
+// prims.hip because every kernel of that unit is pinned by name in an existing budget test.)
+hipError_t launch_rtg_update(const RtgBlob& d, const uint32_t* hmap, const uint32_t* h, const uint8_t* val, uint64_t m,
+                             bool whole, hipStream_t s);
+// idx[j] = handle[idx[j]] for idx[j] < nn, in place (DHT_NONE stays)
+hipError_t launch_rtg_handles(const uint32_t* handle, uint32_t nn, uint32_t* idx, uint64_t m, hipStream_t s);
+
 // ncache.hip: K8w, the resident NodeCache mirror (dhtgpu_nc_*).  The mirror as the kernels read
 // it: device pointers into the context's current buffer set and its accept mask.
 struct NcView {
