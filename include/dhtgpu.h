@@ -583,6 +583,47 @@ int dhtgpu_sr_lists(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t
 int dhtgpu_sr_lists_dev(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
                         uint32_t* out_len, void* stream);
 
+/* ---- K10m: Dht::trySearchInsert over the searches' ordered map ---------------------------------- */
+/* Dht::trySearchInsert (src/dht.cpp:118-150) for a batch of learned nodes over the resident searches
+ * of dhtgpu_sr_*: the reference's searches(af) -- a std::map by target -- is the MAP, a set of slots
+ * the library keeps in ascending order of their targets.  For node j of a batch, each taken strictly
+ * after node j - 1: c = lower_bound(map, id_j); forward over c, c + 1, ... and then backward over
+ * c - 1, c - 2, ...: insertNode(node_j, no token) on the search -- exactly dhtgpu_sr_insert's -- and
+ * stop when it returns false on a search that is neither expired (read after the call) nor done.
+ *
+ * dhtgpu_srm_set: the map is these ns slots, in any order; their targets are gathered and sorted on
+ * the device (the 160-bit radix sort of the cache mirror).  A repeated slot or a slot >= nslots is
+ * DHTGPU_EINVAL; two slots with equal targets are DHTGPU_EUNSORTED and leave the map invalid; ns = 0
+ * is a valid, empty map.  It synchronises.  The map is dropped by dhtgpu_sr_reset and by every
+ * dhtgpu_sr_open (a slot's target may have changed); dhtgpu_sr_expire keeps it, as an expired search
+ * stays in the reference's map.  offer and export return DHTGPU_ENOIDS without a valid map.
+ *
+ * dhtgpu_srm_set_done: Search::done of slot slots[j] = val[j] != 0, kept by the slot until it is
+ * opened again (a new search is not done); stream-ordered, no synchronise, like
+ * dhtgpu_sr_set_candidate.  dhtgpu_sr_status does not report it; dhtgpu_srm_export does.
+ *
+ * dhtgpu_srm_offer: out_cnt[j] = the number of searches that took node j (trySearchInsert's return
+ * value is out_cnt[j] > 0); out_touched (nullable) = a bitmask by slot, ceil(nslots / 32) words,
+ * zeroed by the call, a bit set where the slot took at least one node of the batch -- the searches
+ * whose next step the caller reschedules; out_stats[4] (nullable) = {nodes answered by the filter
+ * without a walk, insertNode calls of the walk, 1 when the batch held a node that is removable and
+ * not expired (then no node is filtered), 1 when a row overflowed}.  m = 0 is a no-op.  The host
+ * form synchronises and returns DHTGPU_ERANGE after applying everything when a row overflowed, as
+ * dhtgpu_sr_insert does; a handle >= DHTGPU_NC_MAX_HANDLE is DHTGPU_EINVAL before any launch.  _dev:
+ * every array on the device (ids as word planes, id_stride >= m), a stream (NULL = the context's);
+ * it neither synchronises nor allocates and reports overflow through the slots' status bits.  The
+ * offers of a context share its work arrays: they are ordered on one stream, or by the caller.
+ *
+ * dhtgpu_srm_export: the map in target order, out_slots[ns] and out_done[ns] (both nullable; sized
+ * by the caller for the ns of the last set), *out_ns = ns.  It synchronises. */
+int dhtgpu_srm_set(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t ns);
+int dhtgpu_srm_set_done(dhtgpu_ctx* ctx, const uint32_t* slots, const uint8_t* val, uint32_t m);
+int dhtgpu_srm_offer(dhtgpu_ctx* ctx, const uint32_t* handles, const uint8_t* ids20, uint32_t m, uint32_t* out_cnt,
+                     uint32_t* out_touched, uint32_t* out_stats);
+int dhtgpu_srm_offer_dev(dhtgpu_ctx* ctx, const uint32_t* handles, const uint32_t* id_planes, uint64_t id_stride,
+                         uint32_t m, uint32_t* out_cnt, uint32_t* out_touched, uint32_t* out_stats, void* stream);
+int dhtgpu_srm_export(dhtgpu_ctx* ctx, uint32_t* out_slots, uint8_t* out_done, uint32_t* out_ns);
+
 /* ---- K2: routing-bucket classification over the context's id set -------------- */
 /* out_bucket[n] (nullable) = findBucket(id) index; hist161[161] = histogram of
  * commonBits(id, myid).  nb in [1, 256], firsts sorted ascending (as in the table). */

@@ -976,6 +976,8 @@ private:
  *   refresh(now)                once per sweep: flushes the queue, then isExpired() | isRemovable(now) << 1
  *                               of every live cache slot, as one upload
  *   refillBatch(searches, slots, q, now)   Dht::refill for q searches; returns the inserted counts
+ *   offerBatch(searches, nodes, n, now)    Dht::trySearchInsert for n learned nodes over the host's
+ *                               std::map of searches (see the method)
  * Below min_device_batch searches refillBatch runs the reference's body on the host
  * (detail::cached_nodes_host on the map, then sr.insertNode) and queues what it inserted: no device
  * call, so one refill costs what the reference's costs.  From the threshold up it flushes the
@@ -991,6 +993,17 @@ private:
  * 283 searches.  The constant is the next multiple of 64 at or above 1.1 x the crossover (311.3):
  * the margin keeps box-to-box spread from putting the default on the losing side. */
 static const size_t kMinResidentRefillBatch = 320;
+/* Smallest batch of learned nodes offerBatch sends to the device (dhtgpu_srm_offer), from the
+ * crossover measured in DESIGN.md §5n (profiles/r15/srmap/srmap_check_bench.txt: offerBatch through
+ * this adapter on the device against the host walk plus the flush of the pairs it queued, 2^20 cached
+ * keys, converged lists).  With 1,024 searches the host route wins at 64 nodes (292.4 against 361.2
+ * us) and the device at 1,024 (2,178 against 3,394 us): the differences cross at 115 nodes.  With
+ * 16,384 searches the host route still wins at 1,024 nodes (2,818 against 3,157 us) and the device at
+ * 16,384 (26,970 against 46,930 us): they cross at 1,280.  The constant is the next multiple of 64 at
+ * or above 1.1 x the larger crossover (1,408), on the device's side for both map sizes.  On fresh
+ * (empty) lists the device lost at both sizes measured (1 and 64 nodes), which this threshold keeps
+ * on the host; larger fresh batches were not measured. */
+static const size_t kMinResidentOfferBatch = 1408;
 
 template <class NodeMap, class SearchT, class Cache = ResidentCache<NodeMap>>
 class ResidentSearches {
@@ -1000,8 +1013,10 @@ public:
     typedef typename std::remove_reference<decltype(std::declval<SearchT&>().nodes[0])>::type SearchNodeT;
     /* map: the NodeCache map the host body walks (it outlives this object) */
     ResidentSearches(Cache& cache, const NodeMap& map, uint32_t nslots = 16384)
-        : min_device_batch(kMinResidentRefillBatch), cache_(cache), map_(map), nslots_(nslots), next_(0), ready_(false) {}
+        : min_device_batch(kMinResidentRefillBatch), min_offer_batch(kMinResidentOfferBatch), cache_(cache), map_(map),
+          nslots_(nslots), next_(0), ready_(false), map_version_(1), sent_version_(0) {}
     size_t min_device_batch;   // smallest batch refilled on the device
+    size_t min_offer_batch;    // smallest batch of learned nodes offered on the device
 
     template <class HashT>
     uint32_t open(const HashT& id) {
@@ -1015,6 +1030,9 @@ public:
         }
         Op op = {kOpen, s, 0, Cache::Slots::key_of(id), NodePtr()};
         log_.push_back(op);
+        slot_of_target_[op.key] = s;
+        target_of_slot_[s] = op.key;
+        ++map_version_;
         return s;
     }
     /* the slot goes to the free list; what was queued for it leaves the queue */
@@ -1024,6 +1042,13 @@ public:
             if (log_[i].slot != slot) log_[w++] = log_[i];
         log_.resize(w);
         free_.push_back(slot);
+        const auto t = target_of_slot_.find(slot);
+        if (t != target_of_slot_.end()) {
+            const auto k = slot_of_target_.find(t->second);
+            if (k != slot_of_target_.end() && k->second == slot) slot_of_target_.erase(k);
+            target_of_slot_.erase(t);
+        }
+        ++map_version_;
     }
     void noteInsert(uint32_t slot, const NodePtr& node, bool has_token) {
         Op op = {kInsert, slot, (uint8_t)(has_token ? 1 : 0), Key(), node};
@@ -1083,42 +1108,43 @@ public:
         if (rc != DHTGPU_ERANGE) check(rc, "sr_refill");   // an overflowed row is still a valid list
         check(dhtgpu_sr_lists(ctx(), slots, (uint32_t)q, rows.data(), nullptr, lens.data()), "sr_lists");
         check(dhtgpu_sr_status(ctx(), slots, (uint32_t)q, st.data()), "sr_status");
-        const auto& sl = cache_.slots().slots_;
         for (size_t i = 0; i < q; ++i) {
-            SearchT& sr = *searches[i];
-            const uint32_t* row = &rows[i * DHTGPU_SR_CAP];
-            // a slot names a listed node when both share their owner: no lock(), no key lookup
-            const auto listed = [&](uint32_t h, size_t j) {
-                const NodePtr& p = sr.nodes[j].node;
-                return p && h < sl.size() && !sl[h].owner_before(p) && !p.owner_before(sl[h]);
-            };
-            bool same = lens[i] == sr.nodes.size();   // the usual outcome: the row is the host list
-            for (uint32_t r = 0; same && r < lens[i]; ++r) same = listed(row[r], r);
-            if (!same) {
-                std::vector<SearchNodeT> nodes;
-                nodes.reserve(lens[i]);
-                size_t cur = 0;   // both lists are in distance order: a kept node is found from here on
-                for (uint32_t r = 0; r < lens[i]; ++r) {
-                    const size_t hn = sr.nodes.size();
-                    size_t k = cur;
-                    while (k < hn && !listed(row[r], k)) ++k;
-                    if (k == hn)
-                        for (k = 0; k < cur && !listed(row[r], k); ++k) {}
-                    if (k < hn && listed(row[r], k)) {
-                        nodes.push_back(std::move(sr.nodes[k]));
-                        sr.nodes[k].node.reset();
-                        if (k >= cur) cur = k + 1;
-                    } else if (NodePtr n = row[r] < sl.size() ? sl[row[r]].lock() : NodePtr()) {
-                        nodes.push_back(SearchNodeT(n));
-                        n->setTime(now);
-                    }
-                }
-                sr.nodes = std::move(nodes);
-            }
-            sr.expired = (st[i * 4 + 3] & 1u) != 0;
+            reconcile(*searches[i], &rows[i * DHTGPU_SR_CAP], lens[i], (st[i * 4 + 3] & 1u) != 0, now);
             inserted[i] = ins[i];
         }
         return inserted;
+    }
+
+    /* Dht::trySearchInsert (src/dht.cpp:118-150) for n learned nodes, in order.  searches: the
+     * reference's searches(af), a std::map<InfoHash, Sp<SearchT>> whose every search was opened here
+     * under its key (SearchT::done is read).  Returns trySearchInsert's result per node; touched
+     * (nullable) gets the searches that took a node -- those whose nextSearchStep the caller edits to
+     * now -- and may name a search more than once.  Below min_offer_batch nodes it runs the
+     * reference's walk on the host map and queues every (search, node) the walk called insertNode on.
+     * From the threshold up it flushes the queues, sends the map when a search was opened or closed
+     * since it was last sent, sends the done bits, runs dhtgpu_srm_offer with the node state of the
+     * last refresh, and reconciles the host searches: the rows of those that took a node, and the
+     * length of every other one (a refusal only cuts a list's tail).  A batch that cannot go to the
+     * device -- a search without a slot, a node the cache does not hold -- and a device error before
+     * the offer was issued both fall back to the host walk. */
+    template <class SearchMap, class TimePoint>
+    std::vector<uint8_t> offerBatch(SearchMap& searches, const NodePtr* nodes, size_t n, TimePoint now,
+                                    std::vector<SearchT*>* touched = nullptr) {
+        std::vector<uint8_t> res(n, 0);
+        if (n == 0) return res;
+        if (n >= min_offer_batch) {
+            bool sent = false;
+            offered_ = false;
+            try {
+                sent = offer_device(searches, nodes, n, now, res, touched);
+            } catch (const Error&) {
+                if (offered_) throw;   // the offer was applied: a failing read-back is the caller's
+                sent_version_ = 0;
+            }
+            if (sent) return res;
+        }
+        for (size_t j = 0; j < n; ++j) res[j] = offer_host(searches, nodes[j], now, touched) ? 1 : 0;
+        return res;
     }
 
 private:
@@ -1131,6 +1157,41 @@ private:
         NodePtr node;   // insert, candidate: the node (its cache slot is looked up when the queue is flushed,
     };                  //   so queueing costs no key lookup; a node the cache dropped meanwhile is skipped)
     dhtgpu_ctx* ctx() const { return cache_.context().get(); }
+    /* a host Search made equal to its device row: nodes becomes the row in its order, keeping the
+     * SearchNode of a node that was listed and making a new one (node->setTime(now)) for a new node */
+    template <class TimePoint>
+    void reconcile(SearchT& sr, const uint32_t* row, uint32_t len, bool expired, TimePoint now) {
+        const auto& sl = cache_.slots().slots_;
+        // a slot names a listed node when both share their owner: no lock(), no key lookup
+        const auto listed = [&](uint32_t h, size_t j) {
+            const NodePtr& p = sr.nodes[j].node;
+            return p && h < sl.size() && !sl[h].owner_before(p) && !p.owner_before(sl[h]);
+        };
+        bool same = len == sr.nodes.size();   // the usual outcome: the row is the host list
+        for (uint32_t r = 0; same && r < len; ++r) same = listed(row[r], r);
+        if (!same) {
+            std::vector<SearchNodeT> nodes;
+            nodes.reserve(len);
+            size_t cur = 0;   // both lists are in distance order: a kept node is found from here on
+            for (uint32_t r = 0; r < len; ++r) {
+                const size_t hn = sr.nodes.size();
+                size_t k = cur;
+                while (k < hn && !listed(row[r], k)) ++k;
+                if (k == hn)
+                    for (k = 0; k < cur && !listed(row[r], k); ++k) {}
+                if (k < hn && listed(row[r], k)) {
+                    nodes.push_back(std::move(sr.nodes[k]));
+                    sr.nodes[k].node.reset();
+                    if (k >= cur) cur = k + 1;
+                } else if (NodePtr n = row[r] < sl.size() ? sl[row[r]].lock() : NodePtr()) {
+                    nodes.push_back(SearchNodeT(n));
+                    n->setTime(now);
+                }
+            }
+            sr.nodes = std::move(nodes);
+        }
+        sr.expired = expired;
+    }
     void ensure() {
         if (ready_) return;
         check(dhtgpu_sr_reset(ctx(), nslots_), "sr_reset");
@@ -1184,12 +1245,108 @@ private:
         check(dhtgpu_sr_set_candidate(ctx(), slots.data(), handles.data(), val.data(), (uint32_t)slots.size()),
               "sr_set_candidate");
     }
+    /* the slot of the search opened for this target (DHTGPU_NONE: none) */
+    template <class HashT>
+    uint32_t slot_of(const HashT& id) const {
+        const auto it = slot_of_target_.find(Cache::Slots::key_of(id));
+        return it == slot_of_target_.end() ? DHTGPU_NONE : it->second;
+    }
+    /* Dht::trySearchInsert's body for one node on the host map; every (search, node) it called
+     * insertNode on is queued, as noteInsert queues a reply's */
+    template <class SearchMap, class TimePoint>
+    bool offer_host(SearchMap& searches, const NodePtr& node, TimePoint now, std::vector<SearchT*>* touched) {
+        bool inserted = false;
+        const auto closest = searches.lower_bound(node->id);
+        const auto visit = [&](typename SearchMap::iterator it) {   // false: the walk stops here
+            SearchT& s = *it->second;
+            const uint32_t slot = slot_of(it->first);
+            const bool added = s.insertNode(node, now);
+            if (slot != DHTGPU_NONE) noteInsert(slot, node, false);
+            if (added) {
+                inserted = true;
+                if (touched) touched->push_back(&s);
+            }
+            return added || s.expired || s.done;
+        };
+        for (auto it = closest; it != searches.end(); ++it)
+            if (!visit(it)) break;
+        for (auto it = closest; it != searches.begin();) {
+            --it;
+            if (!visit(it)) break;
+        }
+        return inserted;
+    }
+    /* The device side of offerBatch.  Returns false -- nothing sent that changes a list -- when the
+     * batch cannot go to the device: a search without a slot, a node the cache does not hold. */
+    template <class SearchMap, class TimePoint>
+    bool offer_device(SearchMap& searches, const NodePtr* nodes, size_t n, TimePoint now, std::vector<uint8_t>& res,
+                      std::vector<SearchT*>* touched) {
+        std::vector<uint32_t> slots, handles(n);
+        std::vector<SearchT*> ptrs;
+        std::vector<uint8_t> done, ids;
+        for (auto it = searches.begin(); it != searches.end(); ++it) {
+            const uint32_t slot = slot_of(it->first);
+            if (slot == DHTGPU_NONE) return false;
+            slots.push_back(slot);
+            ptrs.push_back(&*it->second);
+            done.push_back(it->second->done ? 1 : 0);
+        }
+        for (size_t j = 0; j < n; ++j) {
+            handles[j] = cache_.slots().slotOf(nodes[j]->id);
+            if (handles[j] == DHTGPU_NONE) return false;
+            detail::put_id(ids, nodes[j]->id);
+        }
+        cache_.flush();
+        flush();
+        const uint32_t ns = (uint32_t)slots.size();
+        if (sent_version_ != map_version_ || sent_ns_ != ns) {
+            check(dhtgpu_srm_set(ctx(), slots.empty() ? nullptr : slots.data(), ns), "srm_set");
+            sent_version_ = map_version_;
+            sent_ns_ = ns;
+        }
+        if (ns) check(dhtgpu_srm_set_done(ctx(), slots.data(), done.data(), ns), "srm_set_done");
+        std::vector<uint32_t> cnt(n), mask((nslots_ + 31) / 32 + 1);
+        const int rc = dhtgpu_srm_offer(ctx(), handles.data(), ids.data(), (uint32_t)n, cnt.data(), mask.data(), nullptr);
+        if (rc != DHTGPU_ERANGE) check(rc, "srm_offer");   // an overflowed row is still a valid list
+        offered_ = true;
+        for (size_t j = 0; j < n; ++j) res[j] = cnt[j] > 0;
+        if (!ns) return true;
+        // every mapped search: its length (a refusal cuts the list's tail and sets no bit); the
+        // searches that took a node: their rows
+        std::vector<uint32_t> st(ns * 4), tslots, rows, lens;
+        std::vector<size_t> tidx;
+        check(dhtgpu_sr_status(ctx(), slots.data(), ns, st.data()), "sr_status");
+        for (uint32_t i = 0; i < ns; ++i) {
+            if ((mask[slots[i] >> 5] >> (slots[i] & 31u)) & 1u) {
+                tslots.push_back(slots[i]);
+                tidx.push_back(i);
+            } else if (st[i * 4] < ptrs[i]->nodes.size()) {
+                ptrs[i]->nodes.resize(st[i * 4]);
+            }
+        }
+        if (!tslots.empty()) {
+            rows.resize(tslots.size() * DHTGPU_SR_CAP);
+            lens.resize(tslots.size());
+            check(dhtgpu_sr_lists(ctx(), tslots.data(), (uint32_t)tslots.size(), rows.data(), nullptr, lens.data()), "sr_lists");
+            for (size_t t = 0; t < tslots.size(); ++t) {
+                const size_t i = tidx[t];
+                reconcile(*ptrs[i], &rows[t * DHTGPU_SR_CAP], lens[t], (st[i * 4 + 3] & 1u) != 0, now);
+                if (touched) touched->push_back(ptrs[i]);
+            }
+        }
+        return true;
+    }
     Cache& cache_;
     const NodeMap& map_;
     uint32_t nslots_, next_;
     bool ready_;
     std::vector<uint32_t> free_;
     std::vector<Op> log_;
+    std::map<Key, uint32_t> slot_of_target_;   // the searches' map as the device holds it: target -> slot
+    std::map<uint32_t, Key> target_of_slot_;
+    uint64_t map_version_, sent_version_;      // bumped by open / close; the version dhtgpu_srm_set last sent
+    uint32_t sent_ns_ = 0;
+    bool offered_ = false;                     // offerBatch: dhtgpu_srm_offer returned for this batch
 };
 
 /* Drop-in for NetworkEngine::bufferNodes(af, id, nodes) (src/network_engine.cpp:1003-1032)

@@ -17,6 +17,7 @@ Reference interfaces mirrored (OpenDHT tree paths):
   Context.nc_set / nc_insert / nc_erase / nc_nodes  NodeCache's map resident on the device, changed
                           incrementally; getCachedNodes one wave per target (src/node_cache.cpp:42-123)
   Context.sr_reset / sr_open / sr_insert / sr_refill / sr_status / sr_lists  the searches' node lists
+  Context.srm_set / srm_set_done / srm_offer / srm_export  Dht::trySearchInsert over their ordered map
                           resident on the device: Search::insertNode one wave per search
                           (src/search.h:636-722), Dht::refill fused with getCachedNodes (src/dht.cpp:656-677)
 """
@@ -191,6 +192,11 @@ def lib():
         "dhtgpu_sr_status_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
         "dhtgpu_sr_lists": ([_vp, _u32p, ctypes.c_uint32, _u32p, _u8p, _u32p], ctypes.c_int),
         "dhtgpu_sr_lists_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "dhtgpu_srm_set": ([_vp, _u32p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_srm_set_done": ([_vp, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_srm_offer": ([_vp, _u32p, _u8p, ctypes.c_uint32, _u32p, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_srm_offer_dev": ([_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "dhtgpu_srm_export": ([_vp, _u32p, _u8p, _u32p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("DHTGPU_LIB") and not hasattr(L, name):
@@ -226,7 +232,8 @@ def exported_symbols():
             "dhtgpu_sr_reset", "dhtgpu_sr_open", "dhtgpu_sr_expire", "dhtgpu_sr_set_state", "dhtgpu_sr_update_state",
             "dhtgpu_sr_set_candidate", "dhtgpu_sr_insert", "dhtgpu_sr_insert_dev", "dhtgpu_sr_refill",
             "dhtgpu_sr_refill_dev", "dhtgpu_sr_status", "dhtgpu_sr_status_dev", "dhtgpu_sr_lists",
-            "dhtgpu_sr_lists_dev"]
+            "dhtgpu_sr_lists_dev", "dhtgpu_srm_set", "dhtgpu_srm_set_done", "dhtgpu_srm_offer", "dhtgpu_srm_offer_dev",
+            "dhtgpu_srm_export"]
 
 
 def _ids(a, name="ids"):
@@ -690,6 +697,7 @@ class Context:
     def sr_reset(self, nslots):
         """nslots empty searches; drops any earlier set and the state array."""
         _check(lib().dhtgpu_sr_reset(self._h, nslots), "sr_reset")
+        self._sr_nslots = int(nslots)
 
     def sr_open(self, slots, targets):
         """A new Search (target, empty list, not expired) in each listed slot; stream-ordered."""
@@ -792,6 +800,55 @@ class Context:
     def sr_lists_dev(self, slots_ptr, m, out_handle_ptr, out_flags_ptr=None, out_len_ptr=None, stream=None):
         _check(lib().dhtgpu_sr_lists_dev(self._h, slots_ptr, m, out_handle_ptr, out_flags_ptr, out_len_ptr, stream),
                "sr_lists_dev")
+
+    # ---- K10m: Dht::trySearchInsert over the searches' ordered map -----------------------
+    def srm_set(self, slots):
+        """The searches' map = these slots (any order), sorted by target on the device; EUNSORTED on
+        equal targets, EINVAL on a repeated or unknown slot."""
+        s = self._u32(slots)
+        _check(lib().dhtgpu_srm_set(self._h, _p(s, _u32p) if s.size else None, s.shape[0]), "srm_set")
+
+    def srm_set_done(self, slots, val):
+        """Search::done of slots[j] = val[j] (array or one value for all); stream-ordered."""
+        s = self._u32(slots)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(val), s.shape)).astype(np.uint8).reshape(-1)
+        _check(lib().dhtgpu_srm_set_done(self._h, _p(s, _u32p), _p(v, _u8p), s.shape[0]), "srm_set_done")
+
+    def srm_offer(self, handles, ids):
+        """Dht::trySearchInsert for the nodes in order.  Returns (cnt, touched, stats): (m,) uint32
+        searches that took each node, the (ceil(nslots / 32),) uint32 bitmask of the slots that took
+        one, and {filtered, walk insertNode calls, hazard, overflow}; raises ERANGE (after applying
+        everything) when a row overflowed -- the three results are then in the exception's `result`."""
+        h = self._u32(handles)
+        m = h.shape[0]
+        k = _ids(ids) if m else np.zeros((0, 20), np.uint8)
+        if k.shape[0] != m:
+            raise ValueError("one id per handle")
+        cnt = np.zeros(m, dtype=np.uint32)
+        touched = np.zeros((getattr(self, "_sr_nslots", 0) + 31) // 32, dtype=np.uint32)
+        stats = np.zeros(4, dtype=np.uint32)
+        code = lib().dhtgpu_srm_offer(self._h, _p(h, _u32p), _p(k, _u8p), m, _p(cnt, _u32p),
+                                      _p(touched, _u32p) if touched.size else None, _p(stats, _u32p))
+        if code != 0:
+            e = DhtGpuError(code, "srm_offer")
+            e.result = (cnt, touched, stats)
+            raise e
+        return cnt, touched, stats
+
+    def srm_offer_dev(self, handles_ptr, id_planes_ptr, id_stride, m, out_cnt_ptr, out_touched_ptr=None,
+                      out_stats_ptr=None, stream=None):
+        _check(lib().dhtgpu_srm_offer_dev(self._h, handles_ptr, id_planes_ptr, id_stride, m, out_cnt_ptr, out_touched_ptr,
+                                          out_stats_ptr, stream), "srm_offer_dev")
+
+    def srm_export(self):
+        """The map in target order: (ns,) uint32 slots and (ns,) uint8 done bits."""
+        ns = ctypes.c_uint32(0)
+        _check(lib().dhtgpu_srm_export(self._h, None, None, ctypes.byref(ns)), "srm_export")
+        slots = np.zeros(ns.value, dtype=np.uint32)
+        done = np.zeros(ns.value, dtype=np.uint8)
+        if ns.value:
+            _check(lib().dhtgpu_srm_export(self._h, _p(slots, _u32p), _p(done, _u8p), ctypes.byref(ns)), "srm_export")
+        return slots, done
 
     # ---- a11 / f4: compact node wire format ---------------------------------------
     def buffer_nodes(self, node_tail, af, targets, cand):

@@ -7,7 +7,8 @@
 // everything in order and an early return leaks nothing.
 // Layout: owners and the context; helpers shared by several entry points (each sequence stands
 // once); then the entry points by family -- id set, accept mask, K1, K4, K6, table, caches,
-// wire format, searches, the resident routing table, the resident NodeCache, the resident searches, crawl model.
+// wire format, searches, the resident routing table, the resident NodeCache, the resident searches and their
+// ordered map, crawl model.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
@@ -302,6 +303,23 @@ struct dhtgpu_ctx {
             return SrView{nslots, rows.as<uint32_t>(), (uint64_t)nslots * DHTGPU_SR_CAP, tp.as<uint32_t>(),
                           len.as<uint32_t>(), bits.as<uint8_t>(), st.as<uint8_t>(), nst};
         }
+        // K10m (dhtgpu_srm_*): the searches' ordered map -- the mapped slots in target order and the
+        // sorted target planes -- and an offer's work arrays, all sized by dhtgpu_srm_set so that an
+        // offer allocates nothing.  Dropped by dhtgpu_sr_reset and dhtgpu_sr_open.
+        struct Map {
+            DevBuf in, planes, perm, order, work;
+            uint32_t ns = 0;
+            uint64_t stride = 0;
+            bool valid = false;
+            SrmView view() const { return SrmView{ns, order.as<uint32_t>(), planes.as<uint32_t>(), stride}; }
+            // work: pos | flag | offs | list | trim x 4 | hazard word, the call's own stats
+            SrmWork arrays() const {
+                uint32_t* w = work.as<uint32_t>();
+                return SrmWork{w, w + kSrmChunk, w + 2 * kSrmChunk, w + 3 * kSrmChunk, w + 4 * kSrmChunk,
+                               w + 8 * (size_t)kSrmChunk};
+            }
+            uint32_t* stats() const { return work.as<uint32_t>() + 8 * (size_t)kSrmChunk + 4; }
+        } map;
     } sr;
     // diagnostics: DHTGPU_DBG, the library's one diagnostics switch, read once at creation and
     // masked to kDbgAllowed -- bit 256: per-block phase stamps of F2 / F3 printed to stderr;
@@ -2567,6 +2585,7 @@ int dhtgpu_sr_reset(dhtgpu_ctx* c, uint32_t nslots) {
     DHT_TRY(c->bind());
     dhtgpu_ctx::Searches& t = c->sr;
     t.valid = false;
+    t.map.valid = false;
     DHT_TRY(hipStreamSynchronize(c->stream));
     t.st.release();
     t.st_old.release();
@@ -2589,6 +2608,7 @@ int dhtgpu_sr_open(dhtgpu_ctx* c, const uint32_t* slots, const uint8_t* t20, uin
     if (int r = sr_check(c, slots, m)) return r;
     if (m && !t20) return DHTGPU_EINVAL;
     if (int r = sr_check_slots(c, slots, m, false)) return r;
+    c->sr.map.valid = false;   // a slot's target may change: the ordered map is dropped
     if (!m) return DHTGPU_OK;
     DHT_TRY(c->bind());
     DHT_TRY(c->sr.io.ensure((size_t)m * 4));
@@ -2781,6 +2801,125 @@ int dhtgpu_sr_lists(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t* 
     if (out_flags) DHT_TRY(hipMemcpyAsync(out_flags, p[2], sz[2], hipMemcpyDeviceToHost, c->stream));
     if (out_len) DHT_TRY(hipMemcpyAsync(out_len, p[3], sz[3], hipMemcpyDeviceToHost, c->stream));
     DHT_TRY(hipStreamSynchronize(c->stream));
+    return DHTGPU_OK;
+}
+
+// ---- K10m: Dht::trySearchInsert over the searches' ordered map -------------------------------------
+}  // extern "C"
+
+// The offer of m nodes (device arrays) in chunks of kSrmChunk, each a filter and a walk launch on s;
+// the mask and the counters are zeroed first.  Neither synchronises nor allocates.
+static int srm_offer_on(dhtgpu_ctx* c, const uint32_t* handles, const uint32_t* ip, uint64_t is, uint32_t m,
+                        uint32_t* out_cnt, uint32_t* out_touched, uint32_t* out_stats, hipStream_t s) {
+    const dhtgpu_ctx::Searches::Map& mp = c->sr.map;
+    uint32_t* stats = out_stats ? out_stats : mp.stats();
+    DHT_TRY(hipMemsetAsync(stats, 0, 16, s));
+    if (out_touched && c->sr.nslots) DHT_TRY(hipMemsetAsync(out_touched, 0, (size_t)((c->sr.nslots + 31) / 32) * 4, s));
+    for (uint32_t i = 0; i < m; i += kSrmChunk)
+        DHT_TRY(launch_srm_offer(c->sr.view(), mp.view(), mp.arrays(), handles + i, ip + i, is, std::min(kSrmChunk, m - i),
+                                 out_cnt + i, out_touched, stats, s));
+    return DHTGPU_OK;
+}
+
+extern "C" {
+
+int dhtgpu_srm_set(dhtgpu_ctx* c, const uint32_t* slots, uint32_t ns) {
+    if (int r = sr_check(c, slots, ns)) return r;
+    if (int r = sr_check_slots(c, slots, ns, true)) return r;
+    dhtgpu_ctx::Searches::Map& mp = c->sr.map;
+    mp.valid = false;
+    DHT_TRY(c->bind());
+    DHT_TRY(hipStreamSynchronize(c->stream));   // (an offer in flight reads the buffers replaced below)
+    DHT_TRY(mp.work.ensure(kSrmWorkWords * 4));
+    DHT_TRY(hipMemsetAsync(mp.work.p, 0, kSrmWorkWords * 4, c->stream));
+    mp.ns = ns;
+    mp.stride = pad_ids(ns ? ns : 1);
+    if (ns) {
+        DHT_TRY(mp.in.ensure((size_t)mp.stride * 5 * 4));
+        DHT_TRY(mp.planes.ensure((size_t)mp.stride * 5 * 4));
+        DHT_TRY(mp.perm.ensure((size_t)mp.stride * 4));
+        DHT_TRY(mp.order.ensure((size_t)ns * 4));
+        DHT_TRY(c->sort_scratch.ensure(sort_scratch_bytes(ns)));
+        DHT_TRY(c->sr.io.ensure((size_t)ns * 4));
+        if (int r = sr_upload_slots(c, c->sr.io.as<uint8_t>(), slots, ns)) return r;
+        DHT_TRY(launch_srm_gather(c->sr.view(), c->sr.io.as<uint32_t>(), ns, mp.in.as<uint32_t>(), mp.stride, c->stream));
+        int unique = 1;
+        DHT_TRY(launch_sort_ids(mp.in.as<uint32_t>(), mp.stride, ns, mp.planes.as<uint32_t>(), mp.stride,
+                                mp.perm.as<uint32_t>(), c->sort_scratch.p, &unique, c->stream));
+        DHT_TRY(hipStreamSynchronize(c->stream));
+        if (!unique) return DHTGPU_EUNSORTED;   // a std::map has unique keys: the map stays invalid
+        DHT_TRY(launch_srm_order(c->sr.io.as<uint32_t>(), mp.perm.as<uint32_t>(), ns, mp.order.as<uint32_t>(), c->stream));
+    }
+    mp.valid = true;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_srm_set_done(dhtgpu_ctx* c, const uint32_t* slots, const uint8_t* val, uint32_t m) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && !val) return DHTGPU_EINVAL;
+    if (int r = sr_check_slots(c, slots, m, false)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const uint32_t* d_slots;
+    const uint8_t* d_val;
+    if (int r = stage_idx_val(c, c->sr.io, slots, val, m, &d_slots, &d_val)) return r;
+    DHT_TRY(launch_srm_done(c->sr.view(), d_slots, d_val, m, c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_srm_offer_dev(dhtgpu_ctx* c, const uint32_t* handles, const uint32_t* id_planes, uint64_t id_stride,
+                         uint32_t m, uint32_t* out_cnt, uint32_t* out_touched, uint32_t* out_stats, void* stream) {
+    if (!c || (m && (!handles || !id_planes || !out_cnt))) return DHTGPU_EINVAL;
+    if (!c->sr.valid || !c->sr.map.valid) return DHTGPU_ENOIDS;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    return srm_offer_on(c, handles, id_planes, id_stride, m, out_cnt, out_touched, out_stats, c->stream_or(stream));
+}
+
+int dhtgpu_srm_offer(dhtgpu_ctx* c, const uint32_t* handles, const uint8_t* ids20, uint32_t m, uint32_t* out_cnt,
+                     uint32_t* out_touched, uint32_t* out_stats) {
+    if (!c || (m && (!handles || !ids20 || !out_cnt))) return DHTGPU_EINVAL;
+    if (!c->sr.valid || !c->sr.map.valid) return DHTGPU_ENOIDS;
+    if (!nc_handle_extent(handles, m)) return DHTGPU_EINVAL;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const uint64_t is = pad_q(m);
+    const size_t tw = (size_t)((c->sr.nslots + 31) / 32) * 4;
+    // handles | id planes | counts | touched mask | stats
+    const size_t sz[] = {(size_t)m * 4, (size_t)is * 5 * 4, (size_t)m * 4, tw ? tw : 4, 16};
+    uint8_t* p[5];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    DHT_TRY(hipMemcpyAsync(p[0], handles, sz[0], hipMemcpyHostToDevice, c->stream));
+    if (int r = upload_ids(c, ids20, m, reinterpret_cast<uint32_t*>(p[1]), is)) return r;
+    if (int r = srm_offer_on(c, reinterpret_cast<uint32_t*>(p[0]), reinterpret_cast<uint32_t*>(p[1]), is, m,
+                             reinterpret_cast<uint32_t*>(p[2]), reinterpret_cast<uint32_t*>(p[3]),
+                             reinterpret_cast<uint32_t*>(p[4]), c->stream))
+        return r;
+    uint32_t stats[4] = {0, 0, 0, 0};
+    DHT_TRY(hipMemcpyAsync(out_cnt, p[2], sz[2], hipMemcpyDeviceToHost, c->stream));
+    if (out_touched && tw) DHT_TRY(hipMemcpyAsync(out_touched, p[3], tw, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipMemcpyAsync(stats, p[4], 16, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    if (out_stats) memcpy(out_stats, stats, 16);
+    return stats[3] ? DHTGPU_ERANGE : DHTGPU_OK;
+}
+
+int dhtgpu_srm_export(dhtgpu_ctx* c, uint32_t* out_slots, uint8_t* out_done, uint32_t* out_ns) {
+    if (!c || !out_ns) return DHTGPU_EINVAL;
+    if (!c->sr.valid || !c->sr.map.valid) return DHTGPU_ENOIDS;
+    const dhtgpu_ctx::Searches::Map& mp = c->sr.map;
+    *out_ns = mp.ns;
+    if (!mp.ns || (!out_slots && !out_done)) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    std::vector<uint32_t> order(mp.ns);
+    std::vector<uint8_t> bits(c->sr.nslots);
+    DHT_TRY(hipMemcpyAsync(order.data(), mp.order.p, (size_t)mp.ns * 4, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipMemcpyAsync(bits.data(), c->sr.bits.p, c->sr.nslots, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t j = 0; j < mp.ns; ++j) {
+        if (out_slots) out_slots[j] = order[j];
+        if (out_done) out_done[j] = order[j] < c->sr.nslots ? (bits[order[j]] >> 2) & 1u : 0u;
+    }
     return DHTGPU_OK;
 }
 

@@ -356,7 +356,7 @@ struct SrView {
     uint64_t es;             //   distance to the slot's target, then its handle | flags << 28; es = nslots * 64
     uint32_t* tp;            // target word planes, tp[w * nslots + slot]
     uint32_t* len;           // [nslots] list lengths (<= 64)
-    uint8_t* bits;           // [nslots] bit0 Search::expired, bit1 overflowed
+    uint8_t* bits;           // [nslots] bit0 Search::expired, bit1 overflowed, bit2 Search::done
     const uint8_t* st;       // node state by handle (bit0 isExpired(), bit1 isRemovable(now)), [nst]
     uint32_t nst;            //   a handle at or past nst reads as 0
 };
@@ -378,6 +378,39 @@ hipError_t launch_sr_candidate(const SrView& v, const uint32_t* slots, const uin
 hipError_t launch_sr_status(const SrView& v, const uint32_t* slots, uint32_t m, uint32_t* out4, hipStream_t s);
 hipError_t launch_sr_lists(const SrView& v, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
                            uint32_t* out_len, hipStream_t s);
+
+// srmap.hip: K10m, Dht::trySearchInsert over the searches' ordered map (dhtgpu_srm_*).  The map as
+// the kernels read it: the mapped slots in ascending order of their targets and those targets.
+struct SrmView {
+    uint32_t ns;             // mapped searches
+    const uint32_t* order;   // [ns] slot of the j-th smallest target
+    const uint32_t* tp;      // the sorted targets as word planes, tp[w * ts + j]
+    uint64_t ts;
+};
+constexpr uint32_t kSrmChunk = 16384;   // nodes per filter + walk launch pair (the work arrays' size)
+// The per-node work arrays of one chunk and the call's counters (device, owned by the context).
+struct SrmWork {
+    uint32_t* pos;      // [kSrmChunk] lower bound of the node's id in the map
+    uint32_t* flag;     // [kSrmChunk] 1: the node is walked, 0: the filter answered it
+    uint32_t* offs;     // [kSrmChunk] exclusive scan of flag
+    uint32_t* list;     // [kSrmChunk] the walked nodes, batch order
+    uint32_t* trim;     // [kSrmChunk * 4] a filtered node's {forward slot, cut, backward slot, cut}, DHT_NONE: no search
+    uint32_t* hazard;   // one word per chunk launch: a node of the chunk is removable and not expired
+};
+constexpr size_t kSrmWorkWords = (size_t)kSrmChunk * 8 + 64;
+// planes[w * stride + j] = the target of slot slots[j], j < ns
+hipError_t launch_srm_gather(const SrView& v, const uint32_t* slots, uint32_t ns, uint32_t* planes, uint64_t stride,
+                             hipStream_t s);
+// order[j] = slots[perm[j]], j < ns
+hipError_t launch_srm_order(const uint32_t* slots, const uint32_t* perm, uint32_t ns, uint32_t* order, hipStream_t s);
+// Search::done of slot slots[j] = val[j] != 0 (bit 2 of the slot's bits byte; a slot >= nslots skipped)
+hipError_t launch_srm_done(const SrView& v, const uint32_t* slots, const uint8_t* val, uint32_t m, hipStream_t s);
+// trySearchInsert for nodes [0, m) of a chunk (m <= kSrmChunk), in order: handles, id planes ip / is.
+// out_cnt[j] = searches that took node j; out_touched (nullable) |= the bit of every slot that took a
+// node; stats[4] += {filtered nodes, insertNode calls of the walk}, |= {hazard, overflow}.
+hipError_t launch_srm_offer(const SrView& v, const SrmView& mp, const SrmWork& wk, const uint32_t* handles,
+                            const uint32_t* ip, uint64_t is, uint32_t m, uint32_t* out_cnt, uint32_t* out_touched,
+                            uint32_t* stats, hipStream_t s);
 
 // crawl.hip: crawl-replay model (iterative searches over implicit routing tables)
 uint32_t search_list_cap();

@@ -11,7 +11,7 @@
 // words of the node's DISTANCE to the search's target (id ^ target), so that an ordering test is a
 // plain five-word compare and needs no target, and the node's handle with the entry's flags in bits
 // 28-29 (bit0 candidate, bit1 replied; handles are below 2^28) -- plus the target, the length and a
-// bits byte (bit0 Search::expired, bit1 overflowed) per slot.  Node state (bit0 isExpired(), bit1
+// bits byte (bit0 Search::expired, bit1 overflowed, bit2 Search::done -- srmap.hip's) per slot.  Node state (bit0 isExpired(), bit1
 // isRemovable(now)) is a byte array by handle; a handle at or past its extent reads as 0.
 //
 // k_sr_insert holds entry l of the list in lane l (dead lanes: l >= len), with the entry's state
@@ -35,160 +35,12 @@
 #include "dhtgpu_dev.h"
 #include "dhtgpu_internal.h"
 #include "nc_walk_dev.h"
+#include "sr_row_dev.h"   // SrRow, sr_load / sr_store / sr_trim / sr_insert (shared with srmap.hip)
 
 namespace dhtgpu {
 namespace {
 
 constexpr uint32_t kSrWaves = 4;         // searches per 256-thread workgroup
-constexpr uint32_t kSearchNodes = 14;    // SEARCH_NODES, src/dht.h:308
-constexpr uint32_t kHandleMask = (1u << 28) - 1u;   // DHTGPU_NC_MAX_HANDLE - 1
-constexpr uint32_t kFlagShift = 28;
-
-__device__ __forceinline__ uint64_t low_mask(uint32_t n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
-
-// One search's list across the wave: lane l holds entry l.  len, expired, over and drop are wave-uniform.
-struct SrRow {
-    uint32_t d[DHT_W];   // distance to the target
-    uint32_t h;          // handle
-    uint32_t fs;         // bits 0-1: flags (candidate, replied); bits 8-9: the node's state byte
-    uint32_t len;
-    bool expired, over;
-    bool drop;           // an insertion was dropped in this kernel (over is the slot's sticky bit)
-};
-
-constexpr uint32_t kBadBits = 0x101u;    // SearchNode::isBad: candidate || node->isExpired()
-constexpr uint32_t kRemovable = 0x200u;
-
-__device__ __forceinline__ void sr_load(const SrView& v, uint32_t slot, uint32_t lane, SrRow& r) {
-    r.len = __builtin_amdgcn_readfirstlane(v.len[slot]);
-    const uint32_t bits = __builtin_amdgcn_readfirstlane((uint32_t)v.bits[slot]);
-    r.expired = bits & 1u;
-    r.over = bits & 2u;
-    r.drop = false;
-#pragma unroll
-    for (int w = 0; w < DHT_W; ++w) r.d[w] = 0;
-    r.h = 0;
-    r.fs = 0;
-    if (lane < r.len) {
-        const uint64_t e = (uint64_t)slot * 64 + lane;
-#pragma unroll
-        for (int w = 0; w < DHT_W; ++w) r.d[w] = v.ep[(uint64_t)w * v.es + e];
-        const uint32_t hw = v.ep[(uint64_t)DHT_W * v.es + e];
-        r.h = hw & kHandleMask;
-        r.fs = (hw >> kFlagShift) & 3u;
-        if (r.h < v.nst) r.fs |= (uint32_t)v.st[r.h] << 8;
-    }
-}
-
-__device__ __forceinline__ void sr_store(const SrView& v, uint32_t slot, uint32_t lane, const SrRow& r) {
-    if (lane < r.len) {
-        const uint64_t e = (uint64_t)slot * 64 + lane;
-#pragma unroll
-        for (int w = 0; w < DHT_W; ++w) v.ep[(uint64_t)w * v.es + e] = r.d[w];
-        v.ep[(uint64_t)DHT_W * v.es + e] = r.h | ((r.fs & 3u) << kFlagShift);
-    }
-    if (lane == 0) {
-        v.len[slot] = r.len;
-        v.bits[slot] = (uint8_t)((r.expired ? 1u : 0u) | (r.over ? 2u : 0u));
-    }
-}
-
-// the list cut to its longest prefix with at most SEARCH_NODES non-bad entries: the new length
-__device__ __forceinline__ uint32_t sr_trim(const SrRow& r, uint32_t lane) {
-    const uint64_t good = ~__ballot((r.fs & kBadBits) != 0) & low_mask(r.len);
-    const uint32_t upto = (uint32_t)__popcll(good & low_mask(lane + 1));   // non-bad entries of [0, lane]
-    const uint32_t cut = (uint32_t)__popcll(__ballot(upto <= kSearchNodes));
-    return cut < r.len ? cut : r.len;
-}
-
-// Search::insertNode(x) with x = {distance xd, handle xh, state byte xs, replied with a token xt}
-// (all wave-uniform), then removeExpiredNode when x became a search node.  Returns insertNode's result.
-__device__ __forceinline__ bool sr_insert(SrRow& r, uint32_t lane, const uint32_t* xd, uint32_t xh, uint32_t xs, bool xt) {
-    bool far = false, decided = false;   // x farther than this lane's entry (xorCmp > 0)
-#pragma unroll
-    for (int w = 0; w < DHT_W; ++w) {
-        if (!decided && xd[w] != r.d[w]) {
-            far = xd[w] > r.d[w];
-            decided = true;
-        }
-    }
-    const uint64_t live = low_mask(r.len);
-    const uint64_t same = __ballot(r.h == xh) & live;
-    const uint64_t stop = (__ballot(far) & live) | same;
-    bool found = false;
-    uint32_t n = 0;
-    if (stop) {
-        const uint32_t p = 63u - (uint32_t)__clzll((long long)stop);
-        found = (same >> p) & 1ull;
-        n = found ? p : p + 1;
-    }
-    bool added = false, ok = true;
-    if (!found) {
-        bool full = false;
-        uint32_t tcut = r.len;
-        if (r.expired) {
-            if (r.len >= kSearchNodes) {
-                full = true;
-                tcut = kSearchNodes;
-            }
-        } else {
-            const uint64_t good = ~__ballot((r.fs & kBadBits) != 0) & live;
-            full = (uint32_t)__popcll(good) >= kSearchNodes;
-            tcut = sr_trim(r, lane);
-        }
-        if (full) {
-            r.len = tcut;
-            if (n >= tcut) ok = false;   // farther than every kept node: not inserted
-        }
-        if (ok && r.len >= 64) {         // the row cannot hold the list: flagged, the insertion dropped
-            r.over = r.drop = true;
-            ok = false;
-        }
-        if (ok) {
-            const uint32_t nfs = (xs & 3u) << 8;
-#pragma unroll
-            for (int w = 0; w < DHT_W; ++w) {
-                const uint32_t u = (uint32_t)__shfl_up((int)r.d[w], 1);
-                r.d[w] = lane > n ? u : (lane == n ? xd[w] : r.d[w]);
-            }
-            const uint32_t uh = (uint32_t)__shfl_up((int)r.h, 1), uf = (uint32_t)__shfl_up((int)r.fs, 1);
-            r.h = lane > n ? uh : (lane == n ? xh : r.h);
-            r.fs = lane > n ? uf : (lane == n ? nfs : r.fs);
-            ++r.len;
-            added = true;
-            if (xs & 1u) {               // a bad node: an expired search keeps SEARCH_NODES entries
-                if (r.expired) r.len = r.len < kSearchNodes ? r.len : kSearchNodes;
-                else r.len = sr_trim(r, lane);
-            } else if (r.expired) {      // the reference counts every other entry bad here: no trim
-                r.expired = false;
-            } else {
-                r.len = sr_trim(r, lane);
-            }
-        }
-    }
-    if (ok && xt && n < r.len && nc_lane(r.h, n & 63u) == xh) {   // a reply with a token
-        if (lane == n) r.fs = (r.fs & ~1u) | 2u;
-        r.expired = false;
-    }
-    if (added) {   // Search::removeExpiredNode: the last removable node
-        const uint64_t rm = __ballot((r.fs & kRemovable) != 0) & low_mask(r.len);
-        if (rm) {
-            const uint32_t e = 63u - (uint32_t)__clzll((long long)rm);
-#pragma unroll
-            for (int w = 0; w < DHT_W; ++w) {
-                const uint32_t u = (uint32_t)__shfl_down((int)r.d[w], 1);
-                if (lane >= e) r.d[w] = u;
-            }
-            const uint32_t uh = (uint32_t)__shfl_down((int)r.h, 1), uf = (uint32_t)__shfl_down((int)r.fs, 1);
-            if (lane >= e) {
-                r.h = uh;
-                r.fs = uf;
-            }
-            --r.len;
-        }
-    }
-    return added;
-}
 
 // wave j of the call -> its slot (wave-uniform); false: past the list or not a slot
 __device__ __forceinline__ bool sr_slot(const SrView& v, const uint32_t* __restrict__ slots, uint32_t m, uint32_t* j,
