@@ -58,19 +58,8 @@ def _check(code, what):
         raise DhtGpuError(code, what)
 
 
-def lib():
-    """Load libdhtgpu.so (raises if absent: there is no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(f"libdhtgpu.so not built at {LIB_PATH}: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    try:  # share the HIP runtime with torch when both live in the process
-        import torch  # noqa: F401
-    except Exception:
-        pass
-    L = ctypes.CDLL(LIB_PATH)
-    sig = {
+# Every entry point of include/dhtgpu.h: argument types, result type.
+_SIG = {
         "dhtgpu_strerror": ([ctypes.c_int], ctypes.c_char_p),
         "dhtgpu_device_count": ([ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         "dhtgpu_ctx_create": ([ctypes.c_int, ctypes.POINTER(_vp)], ctypes.c_int),
@@ -197,8 +186,22 @@ def lib():
         "dhtgpu_srm_offer": ([_vp, _u32p, _u8p, ctypes.c_uint32, _u32p, _u32p, _u32p], ctypes.c_int),
         "dhtgpu_srm_offer_dev": ([_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp], ctypes.c_int),
         "dhtgpu_srm_export": ([_vp, _u32p, _u8p, _u32p], ctypes.c_int),
-    }
-    for name, (args, res) in sig.items():
+}
+
+
+def lib():
+    """Load libdhtgpu.so (raises if absent: there is no fallback path)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise ImportError(f"libdhtgpu.so not built at {LIB_PATH}: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    try:  # share the HIP runtime with torch when both live in the process
+        import torch  # noqa: F401
+    except Exception:
+        pass
+    L = ctypes.CDLL(LIB_PATH)
+    for name, (args, res) in _SIG.items():
         if os.environ.get("DHTGPU_LIB") and not hasattr(L, name):
             continue   # an A/B build of an earlier commit (yardstick runs): calling the entry raises
         f = getattr(L, name)
@@ -210,30 +213,7 @@ def lib():
 
 def exported_symbols():
     """Names of every entry point declared in include/dhtgpu.h (for the ABI test)."""
-    return ["dhtgpu_strerror", "dhtgpu_device_count", "dhtgpu_ctx_create", "dhtgpu_ctx_destroy",
-            "dhtgpu_ctx_stream", "dhtgpu_set_ids", "dhtgpu_gen_ids", "dhtgpu_num_ids", "dhtgpu_get_ids",
-            "dhtgpu_ids_dev", "dhtgpu_topk", "dhtgpu_topk_dev", "dhtgpu_merge_dev", "dhtgpu_tie_words_dev",
-            "dhtgpu_merge_ties_dev", "dhtgpu_pack_dev",
-            "dhtgpu_gen_dev", "dhtgpu_find_closest", "dhtgpu_classify", "dhtgpu_classify_dev",
-            "dhtgpu_cached_nodes", "dhtgpu_index_build", "dhtgpu_index_topk_dev", "dhtgpu_index_topk",
-            "dhtgpu_index_build_timed", "dhtgpu_gen_ids_prefix", "dhtgpu_select_prefix_dev",
-            "dhtgpu_batch_topk_dev", "dhtgpu_batch_topk_timed", "dhtgpu_batch_topk", "dhtgpu_table_depth",
-            "dhtgpu_buffer_nodes_dev", "dhtgpu_buffer_nodes", "dhtgpu_deserialize_nodes", "dhtgpu_net_prepare",
-            "dhtgpu_search_batch", "dhtgpu_search_batch_dev", "dhtgpu_set_global_indices", "dhtgpu_set_sub_handles",
-            "dhtgpu_sub_handles_active", "dhtgpu_handles_to_indices_dev", "dhtgpu_set_search_alpha", "dhtgpu_cache_set",
-            "dhtgpu_cache_nodes", "dhtgpu_cache_sorted", "dhtgpu_buffer_nodes_ids", "dhtgpu_batch_events",
-            "dhtgpu_search_insert", "dhtgpu_table_stats", "dhtgpu_set_accept", "dhtgpu_set_accept_bits_dev",
-            "dhtgpu_update_accept", "dhtgpu_num_accepted", "dhtgpu_write_ids", "dhtgpu_batch_plan",
-            "dhtgpu_rt_set", "dhtgpu_rt_set_good", "dhtgpu_rt_update_good", "dhtgpu_rt_find_closest_dev",
-            "dhtgpu_rt_find_closest", "dhtgpu_rt_reply_dev", "dhtgpu_rt_reply", "dhtgpu_rt_closer_dev",
-            "dhtgpu_rt_closer", "dhtgpu_rtg_on_new_node", "dhtgpu_rtg_expire", "dhtgpu_rtg_set_state",
-            "dhtgpu_rtg_update_state", "dhtgpu_rtg_size", "dhtgpu_rtg_export", "dhtgpu_nc_set", "dhtgpu_nc_insert", "dhtgpu_nc_erase", "dhtgpu_nc_update_accept",
-            "dhtgpu_nc_set_accept", "dhtgpu_nc_size", "dhtgpu_nc_export", "dhtgpu_nc_nodes_dev", "dhtgpu_nc_nodes",
-            "dhtgpu_sr_reset", "dhtgpu_sr_open", "dhtgpu_sr_expire", "dhtgpu_sr_set_state", "dhtgpu_sr_update_state",
-            "dhtgpu_sr_set_candidate", "dhtgpu_sr_insert", "dhtgpu_sr_insert_dev", "dhtgpu_sr_refill",
-            "dhtgpu_sr_refill_dev", "dhtgpu_sr_status", "dhtgpu_sr_status_dev", "dhtgpu_sr_lists",
-            "dhtgpu_sr_lists_dev", "dhtgpu_srm_set", "dhtgpu_srm_set_done", "dhtgpu_srm_offer", "dhtgpu_srm_offer_dev",
-            "dhtgpu_srm_export"]
+    return list(_SIG)
 
 
 def _ids(a, name="ids"):

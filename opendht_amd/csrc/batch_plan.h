@@ -201,7 +201,7 @@ size_t batch_clean_bytes(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, u
 // offset of the shared counters in the workspace head: their words 0..3 (the call's statistics, read by
 // batch_read_stats) stay set after a call, so a head laid out with them elsewhere is zeroed again
 size_t batch_ctr_offset(uint64_t n, uint32_t q_plan, uint32_t k, int num_cus, uint32_t nsub = 1, uint32_t pf = 0);
-// The routing rules of a call over a set past one plan (api.hip: batch_run, batch_run_subs).
+// The routing rules of a call over a set past one plan (api_batch.hip: batch_run, batch_run_subs).
 // Sub-partition split of n ids: the smallest s in [1, 8] with 2^s parts of <= 2^24 expected ids.
 uint32_t split_bits(uint64_t n);
 // the set is served over prefix sub-partitions: no one-set plan accepts the call

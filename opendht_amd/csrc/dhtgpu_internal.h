@@ -1,5 +1,5 @@
 // dhtgpu_internal.h -- host-side launch entry points shared between the kernel
-// translation units and the C ABI (api.hip).  Not part of the public ABI.  K6's host-only half --
+// translation units and the C ABI (api*.hip).  Not part of the public ABI.  K6's host-only half --
 // the plane geometry, the plan flags, SubSpec, the size queries batch_supported / batch_bytes /
 // batch_clean_bytes / batch_ctr_offset / small_* and batch_plan_words -- is batch_plan.h.
 #pragma once

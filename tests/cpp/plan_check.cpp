@@ -212,7 +212,7 @@ static Case subs_case(const char* tag, uint64_t n, uint32_t sb, uint32_t q, uint
     return c;
 }
 
-// What dhtgpu_batch_plan reports in word 0 (api.hip, batch_run's order of decisions)
+// What dhtgpu_batch_plan reports in word 0 (api_batch.hip, batch_run's order of decisions)
 static uint32_t route_of(uint64_t n, uint32_t q, uint32_t k, int cus) {
     if (small_supported(n, q, k)) return 0;
     if (needs_subs(cus, n, q, k)) return 2;

@@ -80,6 +80,30 @@ def test_table_depth_vs_oracle():
     assert opendht_amd.table_depth(np.zeros((0, 20), np.uint8), 0) == 0
 
 
+def test_host_units_keep_their_family_state():
+    """The C ABI's host layer is one unit per entry-point family, and a family's
+    state in the context is its unit's alone: c->rt in api_rtable.hip, c->sr in api_rsearch.hip,
+    c->nc in api_ncache.hip -- but for the one documented crossing, the resident searches' refill,
+    which reads nc.valid and nc.view().  Each unit has its static helpers first and then exactly
+    one extern "C" block."""
+    csrc = os.path.join(ROOT, "opendht_amd", "csrc")
+    units = {fn: open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc))
+             if re.fullmatch(r"api\w*\.hip", fn)}
+    assert set(units) == {"api.hip", "api_batch.hip", "api_dht.hip", "api_rtable.hip", "api_ncache.hip", "api_rsearch.hip"}
+
+    def users(member):
+        return {fn for fn, src in units.items() if re.search(r"->" + member + r"\b", src)}
+
+    assert users("rt") == {"api_rtable.hip"}
+    assert users("sr") == {"api_rsearch.hip"}
+    assert users("nc") == {"api_ncache.hip", "api_rsearch.hip"}
+    crossing = re.findall(r"->nc\b(.{0,8})", units["api_rsearch.hip"])
+    assert crossing and all(re.match(r"\.(valid\b|view\(\))", x) for x in crossing), crossing
+    for fn, src in units.items():
+        assert src.count('extern "C" {') == 1, fn
+        assert src.rstrip().endswith('}  // extern "C"'), fn   # nothing stands behind the block
+
+
 def test_production_build_has_no_measurement_switches():
     """The shipped library cannot return different nodes (SURVEY §8(b) error contract): the
     sources carry no result-altering measurement macro (#if/#ifdef on a DHT_* name), the Makefile

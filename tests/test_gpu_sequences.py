@@ -175,7 +175,7 @@ def _others_unchanged(d, fixed, rec, but, after):
 
 def _family_mutations(m):
     """per family: (label, ops) small then large; the large ones make the buffers that family
-    stages through reallocate (sizes from the ensure / carve calls of api.hip):
+    stages through reallocate (sizes from the ensure / carve calls of the api*.hip units):
       ids    gen_ids_prefix over a 2^20-id stream: staging 5 * 4 B * 2^20 = 20 MB, aux 4 B * its select scratch
       cache  200,000 keys: staging 20 B * n = 4 MB, cache_in, sort_scratch = sort_scratch_bytes(200,000)
       rt     70,001 nodes: rt.buf (the RtView pointers move), staging 1.4 MB; rt_update_good of 65,537: staging 5 B * m
@@ -218,7 +218,7 @@ def _family_mutations(m):
 
 def _stateless(d, m, large):
     """The scratch-heavy stateless calls, each checked against the oracle, small or large enough
-    that the shared buffer it stages through must grow (api.hip):
+    that the shared buffer it stages through must grow (api_dht.hip):
       buffer_nodes_ids  200,000 nodes, 3,000 x 32 candidates, af 6: staging 20 B * nn = 4 MB, wire = wire_bytes(...) ~ 5 MB
       deserialize_nodes 2,000 blobs of 8 records: wire (blob, offsets, senders, outputs) ~ 1.3 MB
       search_insert     100,000 nodes, 2,000 searches at cap 64: staging 2 MB, srch ~ 1.3 MB
