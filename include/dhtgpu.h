@@ -35,6 +35,8 @@
  *   dhtgpu_nc_set/_insert/_erase  NodeCache's map (node_cache.h:43) resident on the device, changed
  *                          incrementally (NodeMap::getNode, clearBadNodes: src/node_cache.cpp:87-123)
  *   dhtgpu_nc_nodes        NodeCache::getCachedNodes (src/node_cache.cpp:42-74) over it, one wave per target
+ *   dhtgpu_ncr_find/_get_nodes/_extract  NodeMap::getNode (src/node_cache.cpp:87-111) in batches over it: ids to
+ *                          handles, absent ids emplaced under the caller's free handles, erase that reports its handle
  *   dhtgpu_sr_insert       Search::insertNode (src/search.h:636-722) over node lists resident on the device,
  *                          one wave per search
  *   dhtgpu_sr_refill       Dht::refill (src/dht.cpp:656-677): getCachedNodes over the nc mirror + insertNode, fused
@@ -506,6 +508,46 @@ int dhtgpu_nc_nodes_dev(dhtgpu_ctx* ctx, const uint32_t* t_planes, uint64_t t_st
                         uint32_t* out_handle, uint32_t* out_cnt, void* stream);
 int dhtgpu_nc_nodes(dhtgpu_ctx* ctx, const uint8_t* targets20_be, uint32_t q, uint32_t count, uint32_t* out_handle,
                     uint32_t* out_cnt);
+
+/* ---- K8r: keys to handles over the resident NodeCache ------------------------------------------ */
+/* What NodeCache::NodeMap::getNode does per node (src/node_cache.cpp:87-111; called for every record
+ * of every reply by NetworkEngine::deserializeNodes, src/network_engine.cpp:868, :884), in batches
+ * over the K8w mirror, so that the key -> handle map lives in one place: the library resolves ids
+ * to handles, emplaces the absent ones under handles drawn from the caller's free list, and says
+ * which handle an erase freed.  The dhtgpu_nc_* entry points are unchanged, and these change the
+ * mirror exactly as dhtgpu_nc_insert / dhtgpu_nc_erase do.  All four return DHTGPU_ENOIDS before
+ * the first dhtgpu_nc_set; m == 0 is a no-op.
+ *
+ * dhtgpu_ncr_find is NodeMap::find (getNode(id) :87-97 without its erase of an expired entry):
+ * out_handle[j] = the handle of key j, DHTGPU_NONE when the mirror does not hold it; out_accept[j]
+ * (nullable) = the handle's current accept bit, 0 for an absent key.  Keys may repeat and come in
+ * any order.  The host form synchronises.  The _dev form takes id word planes (any id_stride >= m,
+ * the layout dhtgpu_srm_offer_dev takes) and device outputs, is stream-ordered (NULL = the
+ * context's stream) and neither synchronises nor allocates: a lookup like dhtgpu_nc_nodes_dev,
+ * under the same rule against dhtgpu_nc_insert / _erase (and _ncr_get_nodes / _extract) in flight.
+ * Its handles can go straight to dhtgpu_sr_insert_dev / dhtgpu_srm_offer_dev. */
+int dhtgpu_ncr_find(dhtgpu_ctx* ctx, const uint8_t* ids20, uint32_t m, uint32_t* out_handle, uint8_t* out_accept);
+int dhtgpu_ncr_find_dev(dhtgpu_ctx* ctx, const uint32_t* id_planes, uint64_t id_stride, uint32_t m,
+                        uint32_t* out_handle, uint8_t* out_accept, void* stream);
+/* The emplace of NodeMap::getNode(id, addr, now, confirm, client) (src/node_cache.cpp:99-111) for m
+ * keys in batch order.  A key already in the map: out_handle[j] = its handle, out_new[j] = 0, its
+ * accept bit untouched.  An absent key at its first appearance takes free_handles[r], r = the
+ * number of distinct absent keys before it in the batch: out_new[j] = 1, and the handle's accept
+ * bit becomes accept ? accept[j] != 0 : 1.  A later repeat of that key: the same handle,
+ * out_new[j] = 0, its accept byte ignored (the first wins, as in dhtgpu_nc_insert).  *out_used =
+ * the free handles consumed.  out_new and out_used are nullable.  With more distinct absent keys
+ * than nfree it returns DHTGPU_ERANGE with nothing applied -- *out_used = the number needed, the
+ * other outputs unspecified.  DHTGPU_ERANGE also when n + m >= 2^32 - 1; a free handle >=
+ * DHTGPU_NC_MAX_HANDLE is DHTGPU_EINVAL before any launch; distinct free handles, none of them in
+ * use, are the caller's business.  Synchronous.  The mirror that results is the one
+ * dhtgpu_nc_insert builds when given, for each key, the handle reported here. */
+int dhtgpu_ncr_get_nodes(dhtgpu_ctx* ctx, const uint8_t* ids20, uint32_t m, const uint32_t* free_handles,
+                         uint32_t nfree, const uint8_t* accept, uint32_t* out_handle, uint8_t* out_new,
+                         uint32_t* out_used);
+/* dhtgpu_nc_erase (map.erase(key): getNode(id) :87-97, clearBadNodes :113-123) that says what it
+ * freed: out_handle[j] = the erased key's handle, DHTGPU_NONE for an absent key and for a repeat of
+ * an earlier key of the batch.  Accept bits are left as they are.  Synchronous. */
+int dhtgpu_ncr_extract(dhtgpu_ctx* ctx, const uint8_t* ids20, uint32_t m, uint32_t* out_handle);
 
 /* ---- K10w: the resident searches --------------------------------------------------------------- */
 /* The node lists of a node's searches (Dht::Search::nodes, src/search.h; up to MAX_SEARCHES = 16384)

@@ -761,6 +761,8 @@ private:
  *   noteErase(id)               where NodeMap::getNode(id) / clearBadNodes erase (:87-97, :113-123); queued
  *   flush()                     the queue as one erase call and one insert call (a key inserted and
  *                               erased again between two flushes never reaches the device)
+ *   slotsOfBatch(ids, n)        the handles of n ids (NodeMap::find): the host's key map, or dhtgpu_ncr_find
+ *   getNodeBatch(ids, n, make)  NodeMap::getNode(id, addr, ...) for a reply's records: dhtgpu_ncr_get_nodes
  *   refresh()                   once per batch: lock() && !isExpired() && !isClient() of every live
  *                               slot (src/node_cache.cpp:68-69), as one mask upload
  *   getCachedNodesBatch(map, targets, q, count)   the batch itself
@@ -777,7 +779,13 @@ private:
  * (profiles/r11/ncache/nc_bench_large_m.json, 10^6 keys): an insert of 524,288 keys costs 1,248 us
  * against 1,446 us for the rebuild, one of 10^6 keys 2,132 against 1,809 us; the differences cross
  * at 705,000 keys.  The erase crosses at 789,000 keys. */
+/* kMinResidentFindBatch: smallest batch of ids slotsOfBatch resolves through dhtgpu_ncr_find
+ * instead of the host's key map (profiles/r17/ncresolve/: the host form against m
+ * std::map finds over the same 2^20 keys, same session): the map wins at 256 ids (16.3 against 42.3
+ * us), the device at 512 (43.6 against 51.5 us); the differences cross at 452 ids, and this is the
+ * next multiple of 64 at or above 1.1 x that. */
 static const size_t kMinResidentCacheBatch = 512;
+static const size_t kMinResidentFindBatch = 512;
 static const double kResidentCacheRebuildRatio = 0.705;
 
 /* ResidentCache's handle space, device-free: the slot vector, the free list, the keys held and
@@ -844,6 +852,47 @@ public:
         const auto it = slot_of_.find(key_of(id));
         return it == slot_of_.end() ? DHTGPU_NONE : it->second;
     }
+    /* slotOf for n keys */
+    template <class HashT>
+    std::vector<uint32_t> slotsOf(const HashT* ids, size_t n) const {
+        std::vector<uint32_t> h(n);
+        for (size_t i = 0; i < n; ++i) h[i] = slotOf(ids[i]);
+        return h;
+    }
+    /* The free list dhtgpu_ncr_get_nodes draws from, `count` handles in the order noteInsert would
+     * take them: the last freed slot first, then fresh slot numbers (fewer than count at the
+     * handle bound). */
+    std::vector<uint32_t> offer(size_t count) const {
+        std::vector<uint32_t> f;
+        f.reserve(count);
+        for (size_t i = free_.size(); i > 0 && f.size() < count; --i) f.push_back(free_[i - 1]);
+        for (size_t h = slots_.size(); f.size() < count && h < DHTGPU_NC_MAX_HANDLE; ++h) f.push_back((uint32_t)h);
+        return f;
+    }
+    /* What a dhtgpu_ncr_get_nodes call answered for n keys (handle[], is_new[], `used` handles of
+     * offer()'s list consumed): the batched NodeMap::getNode(id, addr, ...) on the host side.  A new
+     * key's slot takes make_node(j); a key already held returns its node, or, when that has
+     * expired, a node made anew in the same slot (src/node_cache.cpp:104-106).  Returns the nodes. */
+    template <class HashT, class MakeNode>
+    std::vector<NodePtr> adopt(const HashT* ids, size_t n, const uint32_t* handle, const uint8_t* is_new, size_t used,
+                               MakeNode make_node) {
+        const size_t from_free = used < free_.size() ? used : free_.size();
+        free_.resize(free_.size() - from_free);
+        slots_.resize(slots_.size() + (used - from_free));
+        std::vector<NodePtr> out(n);
+        for (size_t j = 0; j < n; ++j) {
+            const uint32_t h = handle[j];
+            if (is_new[j]) {
+                out[j] = make_node(j);
+                slots_[h] = out[j];
+                slot_of_[key_of(ids[j])] = h;
+            } else if (!(out[j] = slots_[h].lock())) {
+                out[j] = make_node(j);
+                slots_[h] = out[j];
+            }
+        }
+        return out;
+    }
     size_t size() const { return slot_of_.size(); }
     size_t pending() const { return ins_.size() + era_.size(); }
 
@@ -863,9 +912,12 @@ public:
     typedef typename Slots::NodeRef NodeRef;
     typedef typename Slots::Key Key;
     explicit ResidentCache(Context& ctx)
-        : min_device_batch(kMinResidentCacheBatch), rebuild_ratio(kResidentCacheRebuildRatio), ctx_(ctx) {}
+        : min_device_batch(kMinResidentCacheBatch), rebuild_ratio(kResidentCacheRebuildRatio),
+          min_find_batch(kMinResidentFindBatch), max_first_offer((size_t)-1), ctx_(ctx) {}
     size_t min_device_batch;   // smallest batch answered from the mirror
     double rebuild_ratio;      // flush(): queued keys / keys held from which the mirror is rebuilt (0: never)
+    size_t min_find_batch;     // smallest batch slotsOfBatch resolves on the device
+    size_t max_first_offer;    // most free handles getNodeBatch offers before it knows how many are needed
 
     void assign(const NodeMap& map) {
         s_.clear();
@@ -938,6 +990,57 @@ public:
                 if (NodePtr n = s_.slots_[h[i * count + r]].lock()) res[i].push_back(n);
         }
         return res;
+    }
+
+    /* The handles of n ids (DHTGPU_NONE: not held): NodeMap::find in a batch.  Below min_find_batch
+     * from the host's key map, from it up flush() then dhtgpu_ncr_find. */
+    template <class HashT>
+    std::vector<uint32_t> slotsOfBatch(const HashT* ids, size_t n) {
+        if (n < min_find_batch) return s_.slotsOf(ids, n);
+        flush();
+        std::vector<uint8_t> b;
+        b.reserve(n * DHTGPU_HASH_LEN);
+        for (size_t i = 0; i < n; ++i) detail::put_id(b, ids[i]);
+        std::vector<uint32_t> h(n);
+        check(dhtgpu_ncr_find(ctx_.get(), b.data(), (uint32_t)n, h.data(), nullptr), "ncr_find");
+        return h;
+    }
+
+    /* NodeMap::getNode(id, addr, now, confirm, client) (src/node_cache.cpp:99-111) for n ids, where
+     * NetworkEngine::deserializeNodes calls it per record (src/network_engine.cpp:868, :884):
+     * flushes, resolves and emplaces on the device under the free list (then fresh slot numbers),
+     * and creates the Node of every new key through make_node(j) -> shared_ptr<Node>.  A new node
+     * that is not acceptable (a client) has its accept bit cleared.  Returns the n nodes. */
+    template <class HashT, class MakeNode>
+    std::vector<NodePtr> getNodeBatch(const HashT* ids, size_t n, MakeNode make_node) {
+        if (n == 0) return std::vector<NodePtr>();
+        flush();
+        std::vector<uint8_t> b;
+        b.reserve(n * DHTGPU_HASH_LEN);
+        for (size_t i = 0; i < n; ++i) detail::put_id(b, ids[i]);
+        std::vector<uint32_t> h(n);
+        std::vector<uint8_t> is_new(n);
+        uint32_t used = 0;
+        std::vector<uint32_t> offer = s_.offer(n < max_first_offer ? n : max_first_offer);
+        for (;;) {
+            const int r = dhtgpu_ncr_get_nodes(ctx_.get(), b.data(), (uint32_t)n, offer.empty() ? nullptr : offer.data(),
+                                               (uint32_t)offer.size(), nullptr, h.data(), is_new.data(), &used);
+            if (r != DHTGPU_ERANGE || used <= offer.size()) {
+                check(r, "ncr_get_nodes");
+                break;
+            }
+            offer = s_.offer(used);   // nothing was applied: again with as many as it needs
+            if (offer.size() < used) throw Error(DHTGPU_ERANGE, "ResidentCache: out of handles");
+        }
+        std::vector<NodePtr> out = s_.adopt(ids, n, h.data(), is_new.data(), used, make_node);
+        std::vector<uint32_t> rej;
+        for (size_t j = 0; j < n; ++j)
+            if (is_new[j] && !s_.accepted(h[j])) rej.push_back(h[j]);
+        if (!rej.empty()) {
+            const std::vector<uint8_t> zero(rej.size(), 0);
+            check(dhtgpu_nc_update_accept(ctx_.get(), rej.data(), zero.data(), (uint32_t)rej.size()), "nc_update_accept");
+        }
+        return out;
     }
 
     const Slots& slots() const { return s_; }

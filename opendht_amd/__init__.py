@@ -16,6 +16,7 @@ Reference interfaces mirrored (OpenDHT tree paths):
                           findClosestNodes + bufferNodes fused; maintainStorage / onAnnounce closeness tests
   Context.nc_set / nc_insert / nc_erase / nc_nodes  NodeCache's map resident on the device, changed
                           incrementally; getCachedNodes one wave per target (src/node_cache.cpp:42-123)
+  Context.ncr_find / ncr_get_nodes / ncr_extract  NodeMap::getNode in batches over it: ids to handles
   Context.sr_reset / sr_open / sr_insert / sr_refill / sr_status / sr_lists  the searches' node lists
   Context.srm_set / srm_set_done / srm_offer / srm_export  Dht::trySearchInsert over their ordered map
                           resident on the device: Search::insertNode one wave per search
@@ -166,6 +167,11 @@ _SIG = {
         "dhtgpu_nc_nodes_dev": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp],
                                 ctypes.c_int),
         "dhtgpu_nc_nodes": ([_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_ncr_find": ([_vp, _u8p, ctypes.c_uint32, _u32p, _u8p], ctypes.c_int),
+        "dhtgpu_ncr_find_dev": ([_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp], ctypes.c_int),
+        "dhtgpu_ncr_get_nodes": ([_vp, _u8p, ctypes.c_uint32, _u32p, ctypes.c_uint32, _u8p, _u32p, _u8p, _u32p],
+                                 ctypes.c_int),
+        "dhtgpu_ncr_extract": ([_vp, _u8p, ctypes.c_uint32, _u32p], ctypes.c_int),
         "dhtgpu_sr_reset": ([_vp, ctypes.c_uint32], ctypes.c_int),
         "dhtgpu_sr_open": ([_vp, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
         "dhtgpu_sr_expire": ([_vp, _u32p, ctypes.c_uint32], ctypes.c_int),
@@ -668,6 +674,54 @@ class Context:
     def nc_nodes_dev(self, t_planes_ptr, t_stride, q, count, out_handle_ptr, out_cnt_ptr, stream=None):
         _check(lib().dhtgpu_nc_nodes_dev(self._h, t_planes_ptr, t_stride, q, count, out_handle_ptr, out_cnt_ptr,
                                          stream), "nc_nodes_dev")
+
+    # ---- K8r: keys to handles over the resident NodeCache ---------------------------
+    def ncr_find(self, ids, accept=False):
+        """NodeMap::find for m keys (any order, repeats allowed): (m,) uint32 handles, NONE where the
+        mirror does not hold the key; with accept=True also (m,) uint8, the handles' accept bits."""
+        ids = _ids(ids) if len(ids) else np.zeros((0, 20), np.uint8)
+        m = ids.shape[0]
+        h = np.full(m, 0xFFFFFFFF, dtype=np.uint32)
+        a = np.zeros(m, dtype=np.uint8) if accept else None
+        _check(lib().dhtgpu_ncr_find(self._h, _p(ids, _u8p), m, _p(h, _u32p), _p(a, _u8p) if accept else None),
+               "ncr_find")
+        return (h, a) if accept else h
+
+    def ncr_find_dev(self, id_planes_ptr, id_stride, m, out_handle_ptr, out_accept_ptr=None, stream=None):
+        _check(lib().dhtgpu_ncr_find_dev(self._h, id_planes_ptr, id_stride, m, out_handle_ptr, out_accept_ptr, stream),
+               "ncr_find_dev")
+
+    def ncr_get_nodes(self, ids, free_handles, accept=None):
+        """NodeMap::getNode's emplace for m keys in batch order, absent keys under free_handles in
+        order: (m,) uint32 handles, (m,) uint8 new bytes, the number of free handles used.  Too few
+        free handles: DhtGpuError (ERANGE) with .needed set, nothing applied."""
+        ids = _ids(ids) if len(ids) else np.zeros((0, 20), np.uint8)
+        m = ids.shape[0]
+        f = np.ascontiguousarray(free_handles, dtype=np.uint32).reshape(-1)
+        a = None
+        if accept is not None:
+            a = np.ascontiguousarray(np.asarray(accept).reshape(-1) != 0, dtype=np.uint8)
+            if a.shape[0] != m:
+                raise ValueError("accept must have one entry per key")
+        h = np.full(m, 0xFFFFFFFF, dtype=np.uint32)
+        new = np.zeros(m, dtype=np.uint8)
+        used = ctypes.c_uint32(0)
+        code = lib().dhtgpu_ncr_get_nodes(self._h, _p(ids, _u8p), m, _p(f, _u32p) if f.size else None, f.shape[0],
+                                          _p(a, _u8p) if a is not None else None, _p(h, _u32p), _p(new, _u8p),
+                                          ctypes.byref(used))
+        if code:
+            err = DhtGpuError(code, "ncr_get_nodes")
+            err.needed = int(used.value)
+            raise err
+        return h, new, int(used.value)
+
+    def ncr_extract(self, ids):
+        """map.erase(key) for m keys: (m,) uint32, the handle each erased key held (NONE: absent, or a
+        repeat of an earlier key of the batch)."""
+        ids = _ids(ids) if len(ids) else np.zeros((0, 20), np.uint8)
+        h = np.full(ids.shape[0], 0xFFFFFFFF, dtype=np.uint32)
+        _check(lib().dhtgpu_ncr_extract(self._h, _p(ids, _u8p), ids.shape[0], _p(h, _u32p)), "ncr_extract")
+        return h
 
     # ---- K10w: the resident searches ------------------------------------------------
     @staticmethod

@@ -1,5 +1,5 @@
-// api_ncache.hip -- the C ABI's resident NodeCache (K8w, dhtgpu_nc_*): the mirror's two buffer
-// sets, its accept mask by handle, incremental insert / erase and the stream-ordered lookups.
+// api_ncache.hip -- the C ABI's resident NodeCache (K8w, dhtgpu_nc_*; K8r, dhtgpu_ncr_*): the mirror's two buffer
+// sets, its accept mask by handle, incremental insert / erase, the stream-ordered lookups, and keys to handles.
 // The one unit that changes the context's nc state (the resident searches read its view).
 #include "api_ctx.h"
 
@@ -40,38 +40,68 @@ static int nc_sort_batch(dhtgpu_ctx* c, const uint8_t* ids20, uint64_t m, uint32
     return DHTGPU_OK;
 }
 
-// insert / erase: sort the batch, rank it, read the kept count (and the result bytes) back, one
-// pass into the other buffer set.
+// What the ncr forms of a mutation add: get_nodes draws its handles from `free` (the first
+// min(nfree, m) are uploaded) instead of taking them from the caller; both report handles.
+struct NcResolve {
+    const uint32_t* free;   // get_nodes: the caller's free handles; extract: null
+    uint32_t nfree;
+    uint32_t* out_handle;   // [m] host
+    uint32_t* out_used;     // nullable
+};
+
+// insert / erase (and get_nodes / extract: rs set): sort the batch, rank it, read the kept count
+// (and the result bytes, and rs's handles) back, one pass into the other buffer set.
 static int nc_mutate(dhtgpu_ctx* c, bool erase, const uint8_t* ids20, const uint32_t* handles, const uint8_t* accept,
-                     uint32_t m, uint8_t* out_res) {
+                     uint32_t m, uint8_t* out_res, const NcResolve* rs = nullptr) {
     dhtgpu_ctx::NCache& t = c->nc;
     const uint64_t ms = pad_ids(m);
     DHT_TRY(t.sorted.ensure((size_t)ms * 5 * 4));
     int unique = 1;   // repeats inside a batch are allowed
     if (int r = nc_sort_batch(c, ids20, m, t.sorted.as<uint32_t>(), ms, &unique)) return r;
     const size_t nb = ((size_t)m + 255) / 256;   // rank | flag | block counts | their scan | kpos | ksrc | total | result bytes
-    const size_t sz[] = {(size_t)m * 4, (size_t)m * 4, nb * 4, nb * 4, (size_t)m * 4, (size_t)m * 4, 4, (size_t)m};
-    uint8_t* p[8];
+    const bool draw = rs && !erase;              // ... | get_nodes: order counts | their scan | total | order | free handles
+    const uint32_t nup = draw ? std::min(rs->nfree, m) : 0;
+    const size_t sz[] = {(size_t)m * 4, (size_t)m * 4, nb * 4, nb * 4, (size_t)m * 4, (size_t)m * 4, 4, (size_t)m,
+                         draw ? nb * 4 : size_t(0), draw ? nb * 4 : size_t(0), draw ? size_t(4) : size_t(0),
+                         draw ? (size_t)m * 4 : size_t(0), (size_t)nup * 4};
+    uint8_t* p[13];
     DHT_TRY(carve(t.work, sz, p));
+    uint32_t* rank = reinterpret_cast<uint32_t*>(p[0]);
+    uint32_t* flag = reinterpret_cast<uint32_t*>(p[1]);
     uint32_t* kpos = reinterpret_cast<uint32_t*>(p[4]);
     uint32_t* ksrc = reinterpret_cast<uint32_t*>(p[5]);
+    if (!erase || rs) DHT_TRY(t.hin.ensure((size_t)m * 4));   // (extract: the freed handles)
     if (!erase) {
-        DHT_TRY(t.hin.ensure((size_t)m * 4));
-        DHT_TRY(hipMemcpyAsync(t.hin.p, handles, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+        if (draw) {
+            if (nup) DHT_TRY(hipMemcpyAsync(p[12], rs->free, (size_t)nup * 4, hipMemcpyHostToDevice, c->stream));
+        } else {
+            DHT_TRY(hipMemcpyAsync(t.hin.p, handles, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+        }
         if (accept) {
             DHT_TRY(t.ain.ensure((size_t)m));
             DHT_TRY(hipMemcpyAsync(t.ain.p, accept, (size_t)m, hipMemcpyHostToDevice, c->stream));
         }
     }
     const NcView v = t.view();
-    DHT_TRY(launch_nc_rank(erase, v, t.sorted.as<uint32_t>(), ms, t.perm.as<uint32_t>(), m,
-                           reinterpret_cast<uint32_t*>(p[0]), reinterpret_cast<uint32_t*>(p[1]),
+    DHT_TRY(launch_nc_rank(erase, v, t.sorted.as<uint32_t>(), ms, t.perm.as<uint32_t>(), m, rank, flag,
                            reinterpret_cast<uint32_t*>(p[2]), reinterpret_cast<uint32_t*>(p[3]), kpos, ksrc,
                            reinterpret_cast<uint32_t*>(p[6]), p[7], c->stream));
+    if (draw)
+        DHT_TRY(launch_ncr_assign(v, t.sorted.as<uint32_t>(), ms, t.perm.as<uint32_t>(), m, rank, flag, p[7],
+                                  reinterpret_cast<uint32_t*>(p[8]), reinterpret_cast<uint32_t*>(p[9]),
+                                  reinterpret_cast<uint32_t*>(p[10]), reinterpret_cast<uint32_t*>(p[11]),
+                                  reinterpret_cast<uint32_t*>(p[12]), nup, t.hin.as<uint32_t>(), c->stream));
+    else if (rs)
+        DHT_TRY(launch_ncr_extract(v, t.perm.as<uint32_t>(), rank, flag, m, t.hin.as<uint32_t>(), c->stream));
     uint32_t kept = 0;
     DHT_TRY(hipMemcpyAsync(&kept, p[6], 4, hipMemcpyDeviceToHost, c->stream));
     if (out_res) DHT_TRY(hipMemcpyAsync(out_res, p[7], (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    if (rs) DHT_TRY(hipMemcpyAsync(rs->out_handle, t.hin.p, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
     DHT_TRY(hipStreamSynchronize(c->stream));
+    if (draw) {
+        if (rs->out_used) *rs->out_used = kept;
+        if (kept > rs->nfree) return DHTGPU_ERANGE;   // nothing applied
+    }
     if (!kept) return DHTGPU_OK;
     const int dst = t.cur ^ 1;
     const uint64_t nn = erase ? (uint64_t)t.n - kept : (uint64_t)t.n + kept;
@@ -79,7 +109,8 @@ static int nc_mutate(dhtgpu_ctx* c, bool erase, const uint8_t* ids20, const uint
     if (erase) {
         DHT_TRY(launch_nc_erase(v, t.set[dst].as<uint32_t>(), t.cap[dst], kpos, kept, c->stream));
     } else {
-        if (int r = nc_mask_ensure(c, handle_extent(handles, m))) return r;
+        // the mask covers the handles the merge writes: the caller's, or the free handles drawn
+        if (int r = nc_mask_ensure(c, draw ? handle_extent(rs->free, kept) : handle_extent(handles, m))) return r;
         DHT_TRY(launch_nc_insert(v, t.set[dst].as<uint32_t>(), t.cap[dst], kpos, ksrc, kept, t.sorted.as<uint32_t>(), ms,
                                  t.perm.as<uint32_t>(), t.hin.as<uint32_t>(), accept ? t.ain.as<uint8_t>() : nullptr,
                                  t.bits.as<uint32_t>(), c->stream));
@@ -214,6 +245,59 @@ int dhtgpu_nc_nodes(dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t coun
                      [&](const uint32_t* tp, uint64_t ts, uint32_t* d_h, uint32_t* d_cnt) {
         return dhtgpu_nc_nodes_dev(c, tp, ts, q, count, d_h, d_cnt, c->stream);
     });
+}
+
+int dhtgpu_ncr_find_dev(dhtgpu_ctx* c, const uint32_t* ip, uint64_t is, uint32_t m, uint32_t* out_handle,
+                        uint8_t* out_accept, void* stream) {
+    if (!c || (m && (!ip || !out_handle || is < m))) return DHTGPU_EINVAL;
+    if (!c->nc.valid) return DHTGPU_ENOIDS;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_ncr_find(c->nc.view(), c->nc.words, ip, is, m, out_handle, out_accept, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_ncr_find(dhtgpu_ctx* c, const uint8_t* ids20, uint32_t m, uint32_t* out_handle, uint8_t* out_accept) {
+    if (!c || (m && (!ids20 || !out_handle))) return DHTGPU_EINVAL;
+    if (!c->nc.valid) return DHTGPU_ENOIDS;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    dhtgpu_ctx::NCache& t = c->nc;
+    const uint64_t ms = pad_ids(m);
+    DHT_TRY(t.in.ensure((size_t)ms * 5 * 4));
+    if (int r = upload_ids(c, ids20, m, t.in.as<uint32_t>(), ms)) return r;
+    const size_t sz[] = {(size_t)m * 4, (size_t)m};
+    uint8_t* p[2];
+    DHT_TRY(carve(t.work, sz, p));
+    if (int r = dhtgpu_ncr_find_dev(c, t.in.as<uint32_t>(), ms, m, reinterpret_cast<uint32_t*>(p[0]),
+                                    out_accept ? p[1] : nullptr, c->stream))
+        return r;
+    DHT_TRY(hipMemcpyAsync(out_handle, p[0], (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_accept) DHT_TRY(hipMemcpyAsync(out_accept, p[1], (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_ncr_get_nodes(dhtgpu_ctx* c, const uint8_t* ids20, uint32_t m, const uint32_t* free_handles, uint32_t nfree,
+                         const uint8_t* accept, uint32_t* out_handle, uint8_t* out_new, uint32_t* out_used) {
+    if (!c || (m && (!ids20 || !out_handle)) || (nfree && !free_handles)) return DHTGPU_EINVAL;
+    if (!c->nc.valid) return DHTGPU_ENOIDS;
+    if ((uint64_t)c->nc.n + m >= 0xFFFFFFFFull) return DHTGPU_ERANGE;   // (before any array is read)
+    if (nfree && !handle_extent(free_handles, nfree)) return DHTGPU_EINVAL;   // nothing applied
+    if (out_used) *out_used = 0;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const NcResolve rs{free_handles, nfree, out_handle, out_used};
+    return nc_mutate(c, false, ids20, nullptr, accept, m, out_new, &rs);
+}
+
+int dhtgpu_ncr_extract(dhtgpu_ctx* c, const uint8_t* ids20, uint32_t m, uint32_t* out_handle) {
+    if (!c || (m && (!ids20 || !out_handle))) return DHTGPU_EINVAL;
+    if (!c->nc.valid) return DHTGPU_ENOIDS;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const NcResolve rs{nullptr, 0, out_handle, nullptr};
+    return nc_mutate(c, true, ids20, nullptr, nullptr, m, nullptr, &rs);
 }
 
 }  // extern "C"

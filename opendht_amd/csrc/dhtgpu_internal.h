@@ -348,6 +348,29 @@ hipError_t launch_nc_handles(const uint32_t* perm, const uint32_t* hin, uint32_t
 // bits [0, nh) from bytes[nh] (device arrays)
 hipError_t launch_nc_bits_pack(const uint8_t* bytes, uint32_t nh, uint32_t* bits, hipStream_t s);
 
+// ncresolve.hip: K8r, keys to handles over the mirror (dhtgpu_ncr_*).
+// k_ncr_find<G> is instantiated for two widths: a batch of at most kNcrWideMaxBatch keys gives every
+// key a whole wave (the fewest rounds: what a small batch waits for), a larger one kNcrNarrowLanes
+// lanes (a wave serves 64 / kNcrNarrowLanes keys: what a large batch's throughput needs).
+// kNcrWideMaxBatch is the measured crossover of the two; tests mirror it.
+constexpr uint32_t kNcrWideLanes = 64, kNcrNarrowLanes = 16;
+constexpr uint32_t kNcrWideMaxBatch = 5040;
+// out_handle[j] = the handle of key j (id planes ip / is, m keys, any order, repeats allowed) or
+// DHT_NONE; out_accept (nullable) [j] = its accept bit (0: absent, or past the mask's mask_words)
+hipError_t launch_ncr_find(const NcView& v, uint64_t mask_words, const uint32_t* ip, uint64_t is, uint32_t m,
+                           uint32_t* out_handle, uint8_t* out_accept, hipStream_t s);
+// After launch_nc_rank(false, ...) on the same sorted batch (res = its result bytes, batch order):
+// hout[i] = the handle of batch key i -- free_handles[r] for the r-th new key in batch order (DHT_NONE
+// when r >= nfree), the resident handle of a present key, the first appearance's handle of a repeat.
+// bsum / boff: one word per 256 keys each, d_total: one word, ord: m words (scratch).
+hipError_t launch_ncr_assign(const NcView& v, const uint32_t* bp, uint64_t bs, const uint32_t* perm, uint32_t m,
+                             const uint32_t* rank, const uint32_t* flag, const uint8_t* res, uint32_t* bsum,
+                             uint32_t* boff, uint32_t* d_total, uint32_t* ord, const uint32_t* free_handles, uint32_t nfree,
+                             uint32_t* hout, hipStream_t s);
+// After launch_nc_rank(true, ...): out[i] = the handle batch key i's erase frees, else DHT_NONE
+hipError_t launch_ncr_extract(const NcView& v, const uint32_t* perm, const uint32_t* rank, const uint32_t* flag,
+                              uint32_t m, uint32_t* out, hipStream_t s);
+
 // rsearch.hip: K10w, the resident searches (dhtgpu_sr_*).  The search set as the kernels see it:
 // device pointers into the context's buffers.
 struct SrView {

@@ -1,0 +1,8 @@
+# k_ncr_find: every batch through a 32-lane form
+s = open("dhtgpu_internal.h").read()
+a = "constexpr uint32_t kNcrWideLanes = 64, kNcrNarrowLanes = 16;"
+b = [l for l in s.splitlines() if l.startswith("constexpr uint32_t kNcrWideMaxBatch = ")]
+assert s.count(a) == 1 and len(b) == 1
+s = s.replace(a, "constexpr uint32_t kNcrWideLanes = 64, kNcrNarrowLanes = 32;")
+s = s.replace(b[0], "constexpr uint32_t kNcrWideMaxBatch = 0;")
+open("dhtgpu_internal.h", "w").write(s)
