@@ -25,7 +25,8 @@ stream -- the caller's, or torch's current stream when the caller passes none --
 must be torch's current stream, because RCCL orders the collectives after it.
 
 Two exchanges: the all-gather (`gather_records`, the north star's: every rank merges every
-target, so every rank holds the same tie rows) and the all-to-all by target slice
+target, so every rank holds the same tie rows -- in an order of its own, so the ranks agree on
+rank 0's list, all-gathered like the all-to-all's) and the all-to-all by target slice
 (`exchange_records`: rank r receives only the records of the targets it owns, shard_range(q,
 world, r), q*k*12 B per GPU whatever the world size; its tie rows are its own, so the tie lists
 are all-gathered and each rank returns the words each owner asked for).
@@ -178,15 +179,22 @@ class LibOps:
 def merge_allgather(ops, rec, gathered, k, out_idx, out_cnt, tx, idx_base, stream=None, group=None):
     """K3 over the all-gathered records (every rank merges every target) + the tie exchange.
     rec: this rank's own (q, k, 3) records (the tie words come from its own id set); gathered:
-    (world, q, k, 3).  Stream-ordered, no host sync."""
+    (world, q, k, 3).  Stream-ordered, no host sync.
+
+    Every rank's K3 lists the same rows but not in the same order (an atomic counter fills the
+    list), and slot s of a rank's words must be the same row on every rank: the lists are
+    all-gathered (1 + TIE_CAP words per rank) and every rank settles rank 0's list.  tx.ties
+    stays this rank's own: its count, the same on every rank, is the overflow flag."""
     world = gathered.shape[0]
     stream = _stream(stream, rec)
     ops.merge(gathered, 0, k, out_idx, out_cnt, tx.ties if world > 1 else None, stream)
     if world == 1:
         return
-    ops.tie_words(rec, idx_base, tx.ties, 0, tx.words[0], stream)
+    gather_records(tx.ties, group, out=tx.ties_all.view(-1))
+    ties = tx.ties_all[0]
+    ops.tie_words(rec, idx_base, ties, 0, tx.words[0], stream)
     gather_records(tx.words[0], group, out=tx.words_in.view(world * TIE_CAP, k, 3))
-    ops.merge_ties(gathered, tx.words_in, 0, k, tx.ties, out_idx, out_cnt, stream)
+    ops.merge_ties(gathered, tx.words_in, 0, k, ties, out_idx, out_cnt, stream)
 
 
 def merge_alltoall(ops, rec, exch, k, tlo, out_idx, out_cnt, tx, idx_base, stream=None, group=None):

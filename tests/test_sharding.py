@@ -211,6 +211,76 @@ def test_tie_overflow_flagged_when_not_settled():
     assert any(ret[r][2] for r in range(world)), dict(ret)
 
 
+class NoRowBaseOps(HostOps):
+    """A wrong k_tie_words, on the host and in bounds: the words of the listed rows as if every
+    owner's slice began at row 0.  The case table must notice it."""
+
+    def tie_words(self, rec, idx_base, ties, row_base, out, stream):
+        HostOps.tie_words(self, rec, idx_base, ties, 0, out, stream)
+
+
+class RankOrderOps(HostOps):
+    """K3's tie list is filled by an atomic counter: the rows it holds are the same wherever the
+    same records are merged, their order is not.  Odd ranks list them the other way round."""
+
+    def merge(self, g, t0, k, out_idx, out_cnt, ties, stream):
+        HostOps.merge(self, g, t0, k, out_idx, out_cnt, ties, stream)
+        if ties is not None and dist.get_rank() % 2:
+            c = min(int(ties[0]), sharding.TIE_CAP)
+            ties[1:1 + c] = ties[1:1 + c].flip(0)
+
+
+_OPS = {"host": HostOps, "no_row_base": NoRowBaseOps, "rank_order": RankOrderOps}
+
+
+def _worker_table(rank, world, port, runs, ret):
+    """runs: (case name, ops name) pairs, every one a lookup of tests/sharded_cases.py on one
+    process group, one set of buffers and one TieExchange per (cap, k)."""
+    import oracle as O
+    import sharded_cases as SC
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    bufs = SC.Bufs([SC.BY_NAME[name] for name, _ in runs], world, rank, "cpu")
+    out = []
+    for name, ops_name in runs:
+        c = SC.BY_NAME[name]
+        ids, tg = SC.data(c)
+        lo, hi = sharding.shard_range(c.n, world, rank)
+        idx, cnt = O.topk(ids[lo:hi], tg, c.k, threads=2)
+        rec = bufs.view("rec", (c.q, c.k, 3))
+        rec.copy_(records_from(ids[lo:hi], lo, idx, cnt))
+        ops = _OPS[ops_name](ids[lo:hi], lo, tg)
+        out.append((ops_name, SC.verdict(c, world, rank, *SC.run(c, world, rank, ops, rec, lo, bufs))))
+    ret[rank] = out
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_case_table_hostops(world):
+    """Every case of tests/sharded_cases.py (the table the GPU test runs through sharding.LibOps)
+    over gloo with the host stand-ins: every rank's rows == the flat top-k, the flag is up exactly
+    where more rows tied than the cap, the tie counts lie within the table's bounds, and some rank
+    overflowed while another did not.  Covers what the tests above do not reach: an overflow on one
+    rank only (E: the others join its settlement) and a TieExchange, with every buffer, reused by a
+    later lookup (H).  Then two changed stand-ins on the same group: case C with tie words that
+    ignore row_base must NOT come out exact (the table tells a wrong slice row apart), and case A
+    with the tie rows listed in another order on odd ranks must (the order of K3's list is no
+    part of its contract)."""
+    import sharded_cases as SC
+    cases = SC.cases_for(world)
+    runs = [(c.name, "host") for c in cases] + [("C", "no_row_base"), ("A", "rank_order")]
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_worker_table, args=(world, _free_port(), runs, ret), nprocs=world, join=True)
+    table = [v for r in range(world) for o, v in ret[r] if o == "host"]
+    over, under = SC.check(table, world)
+    assert over > 0 and under > 0, (over, under)
+    wrong = [v for r in range(world) for o, v in ret[r] if o == "no_row_base"]
+    assert len(wrong) == world and not all(v["exact"] for v in wrong), wrong
+    order = [v for r in range(world) for o, v in ret[r] if o == "rank_order"]
+    assert len(order) == world and all(v["exact"] and 0 < v["count"] <= 256 for v in order), order
+
+
 def merge_records(gathered, targets, k):
     """Reference merge: order all candidates by (first 64 bits of the xor distance, global idx);
     exact for these hash ids (no two candidates share 64 bits)."""
