@@ -111,7 +111,14 @@ int dhtgpu_gen_ids(dhtgpu_ctx* ctx, uint64_t seed, uint64_t start, uint64_t n);
 /* Multi-GPU prefix routing: generate the stream [start, start+n) and keep
  * only the ids whose top pbits bits equal pval, in stream order.  Every result index of
  * the context then refers to the GLOBAL stream (start + i); get_ids/classify use shard
- * order.  pbits <= 16. */
+ * order.  pbits <= 16.  start + n <= 2^32 - 1 else DHTGPU_ERANGE: every index is a uint32
+ * below DHTGPU_NONE.
+ *   The same rule holds for idx_base, the offset that dhtgpu_topk_dev, dhtgpu_index_topk_dev,
+ * dhtgpu_batch_topk_dev, dhtgpu_tie_words_dev and dhtgpu_handles_to_indices_dev add to
+ * context-local indices: idx_base + n <= 2^32 - 1, n = dhtgpu_num_ids (the index space, whatever
+ * an accept mask hides), else the call returns DHTGPU_ERANGE before it launches anything and
+ * writes no output.  It is checked on every context, a prefix shard whose global indices leave
+ * idx_base unused included.  (dhtgpu_batch_topk_timed takes no idx_base: its indices start at 0.) */
 int dhtgpu_gen_ids_prefix(dhtgpu_ctx* ctx, uint64_t seed, uint64_t start, uint64_t n, uint32_t pbits,
                           uint32_t pval);
 /* Prefix shard contexts (dhtgpu_gen_ids_prefix): on != 0 (the default) makes every

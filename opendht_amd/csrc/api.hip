@@ -96,6 +96,12 @@ int check_topk_dev(const dhtgpu_ctx* c, const uint32_t* tp, uint32_t q, uint32_t
     return DHTGPU_OK;
 }
 
+// The idx_base rule of include/dhtgpu.h: every index idx_base + i, i < n, is a uint32 below
+// DHTGPU_NONE.  n is the context's id count (the index space), whatever an accept mask hides.
+int check_idx_base(const dhtgpu_ctx* c, uint32_t idx_base) {
+    return (uint64_t)idx_base + c->n > 0xFFFFFFFFull ? DHTGPU_ERANGE : DHTGPU_OK;
+}
+
 int check_topk_host(const dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, const uint32_t* out_idx,
                     const uint32_t* out_cnt) {
     if (!c || k == 0 || k > DHTGPU_MAX_K || (q && (!t20 || !out_idx || !out_cnt))) return DHTGPU_EINVAL;
@@ -536,6 +542,7 @@ int dhtgpu_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32_t q, 
                     uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base,
                     void* stream) {
     if (int r = check_topk_dev(c, tp, q, k, out_idx, out_cnt, out_rec)) return r;
+    if (int r = check_idx_base(c, idx_base)) return r;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
     dhtgpu_ctx::ActiveSet A;
@@ -561,6 +568,7 @@ int dhtgpu_tie_words_dev(dhtgpu_ctx* c, const uint32_t* rec, uint32_t q, uint32_
                          void* stream) {
     if (!c || !rec || !out_words || k == 0 || k > DHTGPU_MAX_K) return DHTGPU_EINVAL;
     if (!c->has_ids) return DHTGPU_ENOIDS;
+    if (int r = check_idx_base(c, idx_base)) return r;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
     hipStream_t s = c->stream_or(stream);
@@ -640,6 +648,7 @@ int dhtgpu_index_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
                           uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base,
                           void* stream) {
     if (int r = check_topk_dev(c, tp, q, k, out_idx, out_cnt, out_rec)) return r;
+    if (int r = check_idx_base(c, idx_base)) return r;
     if (!c->acc.has_mask && !c->index_valid) return DHTGPU_ENOIDS;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());

@@ -336,6 +336,7 @@ int dhtgpu_batch_topk_dev(dhtgpu_ctx* c, const uint32_t* tp, uint64_t ts, uint32
                           uint32_t* out_idx, uint32_t* out_cnt, uint32_t* out_rec, uint32_t idx_base,
                           void* stream) {
     if (int r = check_topk_dev(c, tp, q, k, out_idx, out_cnt, out_rec)) return r;
+    if (int r = check_idx_base(c, idx_base)) return r;
     if (!q) return DHTGPU_OK;
     DHT_TRY(c->bind());
     return batch_run(c, tp, ts, q, k, out_idx, out_cnt, out_rec, idx_base,
@@ -418,6 +419,7 @@ int dhtgpu_sub_handles_active(dhtgpu_ctx* c, uint32_t q, uint32_t k) {
 int dhtgpu_handles_to_indices_dev(dhtgpu_ctx* c, const uint32_t* handles, uint64_t m, uint32_t* out_idx,
                                   uint32_t idx_base, void* stream) {
     if (!c || (m && (!handles || !out_idx))) return DHTGPU_EINVAL;
+    if (int r = check_idx_base(c, idx_base)) return r;
     if (!c->subs_valid) return DHTGPU_EINVAL;   // no sub-partitioned call has built the handle space
     if (!m) return DHTGPU_OK;
     DHT_TRY(c->bind());

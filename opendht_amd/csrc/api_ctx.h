@@ -419,6 +419,7 @@ int grow_kept(dhtgpu_ctx* c, DevBuf& cur, DevBuf& old, size_t live, size_t need,
 int local_rows(uint32_t* out_rec, DevBuf& idx, DevBuf& cnt, uint32_t q, uint32_t k, uint32_t** li, uint32_t** lc);
 int check_topk_dev(const dhtgpu_ctx* c, const uint32_t* tp, uint32_t q, uint32_t k, const uint32_t* out_idx,
                    const uint32_t* out_cnt, const uint32_t* out_rec);
+int check_idx_base(const dhtgpu_ctx* c, uint32_t idx_base);
 int check_topk_host(const dhtgpu_ctx* c, const uint8_t* t20, uint32_t q, uint32_t k, const uint32_t* out_idx,
                     const uint32_t* out_cnt);
 // K1 over an active set (K6 falls back to it) and the K4 index build (the crawl model's, too)
