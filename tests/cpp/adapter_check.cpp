@@ -13,13 +13,9 @@
 
 #include "dhtgpu.hpp"
 #include "../../oracle/dht_oracle.h"
+#include "mock_dht.h"
 
 namespace mock {
-struct InfoHash {
-    std::array<uint8_t, 20> d;
-    const uint8_t* data() const { return d.data(); }
-    bool operator<(const InfoHash& o) const { return std::memcmp(d.data(), o.d.data(), 20) < 0; }
-};
 struct Node {
     InfoHash id;
     bool good, expired, client;
@@ -27,15 +23,12 @@ struct Node {
     bool isExpired() const { return expired; }
     bool isClient() const { return client; }
 };
-struct Bucket {
-    InfoHash first;
-    std::list<std::shared_ptr<Node>> nodes;
-};
-typedef std::list<Bucket> RoutingTable;
 }  // namespace mock
+typedef mock::Bucket<std::shared_ptr<mock::Node>> Bucket;
+typedef mock::RoutingTable<std::shared_ptr<mock::Node>> RoutingTable;
 
-static uint64_t rng_state = 88172645463325252ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)rng_state; }
+static mock::Xorshift rng = {88172645463325252ull};
+static uint32_t rnd() { return (uint32_t)rng.step(); }
 
 int main(int argc, char** argv) {
     const bool host_only = argc >= 2 && std::strcmp(argv[1], "--host") == 0;
@@ -51,9 +44,9 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> off(nb + 1);
     orc_table_export(t, firsts.data(), off.data(), nodes.data());
     orc_table_free(t);
-    mock::RoutingTable table;
+    RoutingTable table;
     for (uint32_t b = 0; b < nb; ++b) {
-        mock::Bucket bk;
+        Bucket bk;
         std::memcpy(bk.first.d.data(), &firsts[20 * b], 20);
         for (uint32_t i = off[b]; i < off[b + 1]; ++i) {
             auto n = std::make_shared<mock::Node>();

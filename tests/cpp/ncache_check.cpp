@@ -18,13 +18,9 @@
 
 #include "dhtgpu.hpp"
 #include "../../oracle/dht_oracle.h"
+#include "mock_dht.h"
 
 namespace mock {
-struct InfoHash {
-    std::array<uint8_t, 20> d;
-    const uint8_t* data() const { return d.data(); }
-    bool operator<(const InfoHash& o) const { return std::memcmp(d.data(), o.d.data(), 20) < 0; }
-};
 struct Node {
     InfoHash id;
     bool expired, client;
@@ -34,8 +30,8 @@ struct Node {
 typedef std::map<InfoHash, std::weak_ptr<Node>> NodeMap;
 }  // namespace mock
 
-static uint64_t rng_state = 88172645463325252ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)rng_state; }
+static mock::Xorshift rng = {88172645463325252ull};
+static uint32_t rnd() { return (uint32_t)rng.step(); }
 
 typedef std::shared_ptr<mock::Node> NodeSp;
 

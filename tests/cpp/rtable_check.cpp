@@ -9,8 +9,6 @@
 //                   count
 //   --run           on a GPU: the device paths of ResidentTable against its host paths and the
 //                   oracle, and the host cost per target of a reply (the threshold's host side)
-#include <netinet/in.h>
-
 #include <array>
 #include <chrono>
 #include <cstdio>
@@ -21,18 +19,9 @@
 
 #include "dhtgpu.hpp"
 #include "../../oracle/dht_oracle.h"
+#include "mock_dht.h"
 
 namespace mock {
-struct InfoHash {
-    std::array<uint8_t, 20> d;
-    const uint8_t* data() const { return d.data(); }
-};
-struct SockAddr {
-    sockaddr_in v4;
-    sockaddr_in6 v6;
-    const sockaddr_in& getIPv4() const { return v4; }
-    const sockaddr_in6& getIPv6() const { return v6; }
-};
 struct Node {
     InfoHash id;
     SockAddr addr;
@@ -40,23 +29,20 @@ struct Node {
     bool isGood(long) const { return good; }
     const SockAddr& getAddr() const { return addr; }
 };
-struct Bucket {
-    InfoHash first;
-    std::list<std::shared_ptr<Node>> nodes;
-};
-typedef std::list<Bucket> RoutingTable;
 }  // namespace mock
+typedef mock::Bucket<std::shared_ptr<mock::Node>> Bucket;
+typedef mock::RoutingTable<std::shared_ptr<mock::Node>> RoutingTable;
 
-static uint64_t rng_state = 88172645463325252ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)rng_state; }
+static mock::Xorshift rng = {88172645463325252ull};
+static uint32_t rnd() { return (uint32_t)rng.step(); }
 
 // a snapshot (the arguments of orc_find_closest) as the mock table; tails (nullable): alen + 2
 // bytes per node, copied into the address family's sockaddr
-static mock::RoutingTable make_table(uint32_t nb, const uint8_t* firsts, const uint32_t* off, const uint8_t* nodes,
-                                     const uint8_t* good, const uint8_t* tails, uint32_t alen) {
-    mock::RoutingTable table;
+static RoutingTable make_table(uint32_t nb, const uint8_t* firsts, const uint32_t* off, const uint8_t* nodes,
+                               const uint8_t* good, const uint8_t* tails, uint32_t alen) {
+    RoutingTable table;
     for (uint32_t b = 0; b < nb; ++b) {
-        mock::Bucket bk;
+        Bucket bk;
         std::memcpy(bk.first.d.data(), firsts + 20 * b, 20);
         for (uint32_t i = off[b]; i < off[b + 1]; ++i) {
             auto n = std::make_shared<mock::Node>();
@@ -94,7 +80,7 @@ static int check_tables(const char* path) {
             std::fread(off.data(), 4, nb + 1, f) != nb + 1 || std::fread(nodes.data(), 20, nn, f) != nn ||
             std::fread(good.data(), 1, nn, f) != nn || std::fread(tg.data(), 20, q, f) != q)
             return 2;
-        const mock::RoutingTable table = make_table(nb, firsts.data(), off.data(), nodes.data(), good.data(), nullptr, 0);
+        const RoutingTable table = make_table(nb, firsts.data(), off.data(), nodes.data(), good.data(), nullptr, 0);
         for (uint32_t i = 0; i < q; ++i) {
             mock::InfoHash t;
             std::memcpy(t.d.data(), &tg[20 * i], 20);
@@ -150,7 +136,7 @@ int main(int argc, char** argv) {
     for (uint32_t alen : {4u, 16u}) {
         std::vector<uint8_t> tails((size_t)nn * (alen + 2));
         for (auto& b : tails) b = (uint8_t)rnd();
-        const mock::RoutingTable table = make_table(nb, firsts.data(), off.data(), nodes.data(), good.data(), tails.data(), alen);
+        const RoutingTable table = make_table(nb, firsts.data(), off.data(), nodes.data(), good.data(), tails.data(), alen);
         const uint32_t pairs[2][2] = {{8, 1}, {14, 8}};
         // the oracle's answers
         std::vector<std::vector<uint8_t>> want_reply(q);
@@ -174,7 +160,7 @@ int main(int argc, char** argv) {
         }
         if (host_only) continue;
         dhtgpu::Context ctx(0);
-        dhtgpu::ResidentTable<mock::RoutingTable, long> rt(ctx, my);
+        dhtgpu::ResidentTable<RoutingTable, long> rt(ctx, my);
         rt.assign(table, alen == 4 ? 4 : 6, 1);
         rt.refresh(table, 0L);
         for (int dflt = 0; dflt < 2; ++dflt) {   // the device, then the default dispatch

@@ -8,8 +8,6 @@
 //                   printed -- the test compares them with the Python model's
 //   --run           on a GPU: the mirror follows the mock table through notes and flushes; the
 //                   device paths of ResidentTable against its host paths after every few steps
-#include <netinet/in.h>
-
 #include <array>
 #include <cstdio>
 #include <cstring>
@@ -19,18 +17,9 @@
 
 #include "dhtgpu.hpp"
 #include "../../oracle/dht_oracle.h"
+#include "mock_dht.h"
 
 namespace mock {
-struct InfoHash {
-    std::array<uint8_t, 20> d;
-    const uint8_t* data() const { return d.data(); }
-};
-struct SockAddr {
-    sockaddr_in v4;
-    sockaddr_in6 v6;
-    const sockaddr_in& getIPv4() const { return v4; }
-    const sockaddr_in6& getIPv6() const { return v6; }
-};
 struct Node {
     InfoHash id;
     SockAddr addr;
@@ -42,12 +31,9 @@ struct Node {
     const SockAddr& getAddr() const { return addr; }
 };
 typedef std::shared_ptr<Node> NodePtr;
-struct Bucket {
-    InfoHash first;
-    std::list<NodePtr> nodes;
-};
-typedef std::list<Bucket> RoutingTable;
 }  // namespace mock
+typedef mock::Bucket<mock::NodePtr> Bucket;
+typedef mock::RoutingTable<mock::NodePtr> RoutingTable;
 
 enum { kNone = 0, kKnown = 1, kPlaced = 2, kReplaced = 3, kFull = 4 };
 
@@ -61,10 +47,10 @@ static int lowbit(const mock::InfoHash& h) {
 }
 
 struct HostTable {
-    mock::RoutingTable t;
+    RoutingTable t;
     mock::InfoHash myid;
     bool is_client;
-    typedef mock::RoutingTable::iterator It;
+    typedef RoutingTable::iterator It;
 
     It find_bucket(const mock::InfoHash& id) {
         if (t.empty()) return t.end();
@@ -85,7 +71,7 @@ struct HostTable {
     }
     void split(It b) {
         const unsigned bit = depth(b);
-        mock::Bucket nb;
+        Bucket nb;
         nb.first = b->first;
         nb.first.d[bit / 8] |= (uint8_t)(0x80 >> (bit % 8));
         t.insert(std::next(b), nb);
@@ -139,7 +125,7 @@ static HostTable one_bucket(const uint8_t* myid, bool client) {
     HostTable h;
     std::memcpy(h.myid.d.data(), myid, 20);
     h.is_client = client;
-    mock::Bucket b;
+    Bucket b;
     b.first.d.fill(0);
     h.t.push_back(b);
     return h;
@@ -197,7 +183,7 @@ static int host_ops(const char* path) {
 }
 
 static int run() {
-    typedef dhtgpu::ResidentTable<mock::RoutingTable, long> Resident;
+    typedef dhtgpu::ResidentTable<RoutingTable, long> Resident;
     int bad = 0;
     for (int client = 0; client < 2; ++client) {
         std::vector<uint8_t> myid(20), ids(20 * 3000), tg(20 * 96);

@@ -20,14 +20,10 @@
 
 #include "dhtgpu.hpp"
 #include "../../oracle/dht_oracle.h"
+#include "mock_dht.h"
 
 namespace mock {
 typedef int time_point;
-struct InfoHash {
-    std::array<uint8_t, 20> d;
-    const uint8_t* data() const { return d.data(); }
-    bool operator<(const InfoHash& o) const { return std::memcmp(d.data(), o.d.data(), 20) < 0; }
-};
 struct Node {
     InfoHash id;
     bool expired, client, removable;
@@ -38,101 +34,13 @@ struct Node {
     bool isRemovable(time_point) const { return removable; }
     void setTime(time_point t) { time = t; }
 };
-typedef std::shared_ptr<Node> NodeSp;
-typedef std::map<InfoHash, std::weak_ptr<Node>> NodeMap;
-
-struct SearchNode {
-    NodeSp node;
-    bool candidate;
-    SearchNode() : node(), candidate(false) {}
-    SearchNode(const SearchNode&) = delete;
-    SearchNode(SearchNode&&) = default;
-    SearchNode& operator=(SearchNode&&) = default;
-    SearchNode(const NodeSp& n) : node(n), candidate(false) {}
-    bool isBad() const { return !node || node->isExpired() || candidate; }
-};
-
-static int xor_cmp(const InfoHash& t, const InfoHash& a, const InfoHash& b) {
-    for (int i = 0; i < 20; ++i) {
-        const uint8_t x = a.d[i] ^ t.d[i], y = b.d[i] ^ t.d[i];
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return 0;
-}
-
-// Dht::Search with insertNode written after the oracle's restatement (oracle/dht_oracle.cpp, OrcSearch)
-struct Search {
-    static const size_t kSearchNodes = 14;
-    InfoHash id;
-    bool expired, done;
-    std::vector<SearchNode> nodes;
-    size_t index;   // in the oracle's arrays
-    Search() : expired(false), done(false), index(0) {}
-    bool insertNode(const NodeSp& snode, time_point now) {
-        bool found = false;
-        size_t n = nodes.size();
-        while (n != 0) {
-            --n;
-            if (nodes[n].node == snode) { found = true; break; }
-            if (xor_cmp(id, snode->id, nodes[n].node->id) > 0) { ++n; break; }
-        }
-        if (found) return false;
-        size_t t = nodes.size(), bad = 0;
-        bool full = false;
-        if (expired) {
-            if (nodes.size() >= kSearchNodes) { full = true; t = kSearchNodes; }
-        } else {
-            for (const auto& sn : nodes) bad += sn.isBad();
-            full = nodes.size() - bad >= kSearchNodes;
-            while (t - bad > kSearchNodes) {
-                --t;
-                if (nodes[t].isBad()) bad--;
-            }
-        }
-        if (full) {
-            if (t != nodes.size()) nodes.resize(t);
-            if (n >= t) return false;
-        }
-        nodes.insert(nodes.begin() + n, SearchNode(snode));
-        snode->setTime(now);
-        if (snode->isExpired()) {
-            if (!expired) bad++;
-        } else if (expired) {
-            bad = nodes.size() - 1;
-            expired = false;
-        }
-        while (nodes.size() - bad > kSearchNodes) {
-            if (!expired && nodes.back().isBad()) bad--;
-            nodes.pop_back();
-        }
-        for (size_t e = nodes.size(); e != 0;) {
-            --e;
-            if (nodes[e].node->isRemovable(now)) {
-                nodes.erase(nodes.begin() + e);
-                break;
-            }
-        }
-        return true;
-    }
-};
-typedef std::map<InfoHash, std::shared_ptr<Search>> SearchMap;
-
-// ResidentSearches' view of a cache when no device is there: the slots only
-struct HostCache {
-    typedef dhtgpu::CacheSlots<Node> Slots;
-    typedef Slots::NodePtr NodePtr;
-    typedef Slots::Key Key;
-    Slots s;
-    const Slots& slots() const { return s; }
-    void flush() {}
-    dhtgpu::Context& context() const { throw dhtgpu::Error(DHTGPU_EDEVICE, "no device in this check"); }
-};
 }  // namespace mock
+#include "mock_search.h"
 
 using mock::NodeSp;
 
-static uint64_t rng_state = 88172645463325252ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)rng_state; }
+static mock::Xorshift rng = {88172645463325252ull};
+static uint32_t rnd() { return (uint32_t)rng.step(); }
 
 // The oracle's side: every search as a row of node-table indices advanced by orc_search_insert, and
 // trySearchInsert walked over the searches in target order.

@@ -539,9 +539,5 @@ def test_context_close_returns_device_memory():
 def test_cpp_accept_adapter_on_gpu(tmp_path):
     """ClosestIndex::set_accept_good + query against a host brute force with detail::xor_closer
     (tests/cpp/accept_check.cpp --run: 5,000 nodes, 2,000 targets)."""
-    import subprocess
-    from test_accept_cpu import build_accept_check
-    exe = build_accept_check(str(tmp_path / "accept_check"))
-    out = subprocess.run([exe, "--run"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "0 mismatches" in out.stdout
+    import cpp_check
+    cpp_check.run(cpp_check.build("accept", tmp_path), ["--run"], "accept_check", 120)

@@ -2,8 +2,6 @@
 getCachedNodes and the one-pass insert / erase against the model of ncache_cases.py (a dict and the
 CPU oracle O.cached_nodes_batch) and against dhtgpu_cache_set + dhtgpu_cache_nodes.  Every
 comparison is exact.  Marked gpu: run on the MI355X box."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -422,12 +420,5 @@ def test_isolation_from_the_other_families(ctx, keysets):
 def test_cpp_adapter_resident_cache(tmp_path):
     """dhtgpu::ResidentCache on both dispatch paths against the oracle through insert / erase /
     expiry rounds (tests/cpp/ncache_check.cpp)"""
-    import opendht_amd
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe, libdir, odir = str(tmp_path / "ncache_check"), os.path.dirname(opendht_amd.LIB_PATH), os.path.join(root, "oracle")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "ncache_check.cpp"), "-o", exe, "-L", libdir, "-ldhtgpu",
-                           "-L", odir, "-loracle", "-Wl,-rpath," + libdir, "-Wl,-rpath," + odir])
-    out = subprocess.run([exe, "--run"], capture_output=True, text=True, timeout=120)
-    print(out.stdout)
-    assert out.returncode == 0 and "ncache_check: 0 mismatches" in out.stdout, out.stdout + out.stderr
+    import cpp_check
+    cpp_check.run(cpp_check.build("ncache", tmp_path), ["--run"], "ncache_check", 120)

@@ -1,8 +1,6 @@
 """GPU parity of keys-to-handles over the resident NodeCache (dhtgpu_ncr_*, opendht_amd/csrc/ncresolve.hip):
 the lane-group find, get_nodes and extract against the model of ncresolve_cases.py (the sequential
 loops of NodeMap::getNode over a dict).  Every comparison is exact.  Marked gpu: run on the MI355X box."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -378,12 +376,5 @@ def test_isolation_from_the_table_and_the_searches(ctx, keysets):
 def test_cpp_adapter_get_node_batch(tmp_path):
     """dhtgpu::ResidentCache::getNodeBatch / slotsOfBatch / noteErase rounds against std::map, the
     mirror exported and compared, the retry on too few handles (tests/cpp/ncresolve_check.cpp)"""
-    import opendht_amd
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe, libdir, odir = str(tmp_path / "ncresolve_check"), os.path.dirname(opendht_amd.LIB_PATH), os.path.join(root, "oracle")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "ncresolve_check.cpp"), "-o", exe, "-L", libdir, "-ldhtgpu",
-                           "-L", odir, "-loracle", "-Wl,-rpath," + libdir, "-Wl,-rpath," + odir])
-    out = subprocess.run([exe, "--run"], capture_output=True, text=True, timeout=120)
-    print(out.stdout)
-    assert out.returncode == 0 and "ncresolve_check: 0 mismatches" in out.stdout, out.stdout + out.stderr
+    import cpp_check
+    cpp_check.run(cpp_check.build("ncresolve", tmp_path), ["--run"], "ncresolve_check", 120)

@@ -402,12 +402,8 @@ def test_sharded_records_merge(ctx):
 def test_cpp_adapter_on_gpu(tmp_path):
     """The C++11 drop-in adapter (include/dhtgpu.hpp) over reference-shaped types returns
     the same nodes, in the same order, as the oracle restatements."""
-    import subprocess
-    from test_abi import build_adapter_check
-    exe = build_adapter_check(str(tmp_path / "adapter_check"))
-    out = subprocess.run([exe, "--run"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "0 mismatches" in out.stdout
+    import cpp_check
+    cpp_check.run(cpp_check.build("adapter", tmp_path), ["--run"], "adapter_check", 120)
 
 
 @pytest.mark.parametrize("pbits,pval", [(0, 0), (1, 1), (3, 5)])

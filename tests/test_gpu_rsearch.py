@@ -3,8 +3,6 @@ insertNode, the fused Dht::refill and the small kernels against the model of rse
 oracle's search_insert and getCachedNodes walk).  Every comparison is exact: rows, flags, lengths,
 `expired`, added / inserted and the status words, after every step of every script.  Marked gpu: run
 on the MI355X box."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,7 +14,6 @@ import rsearch_cases as RS
 pytestmark = pytest.mark.gpu
 
 EINVAL, ENOIDS, ERANGE = -1, -4, -6
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -296,12 +293,5 @@ def test_argument_errors():
 def test_cpp_adapter_on_device(tmp_path):
     """tests/cpp/rsearch_check.cpp --run: dhtgpu::ResidentSearches on mock Search / SearchNode / Node
     types, refillBatch on both sides of its threshold against the oracle."""
-    import opendht_amd
-    exe = str(tmp_path / "rsearch_check")
-    libdir = os.path.dirname(opendht_amd.LIB_PATH)
-    odir = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "rsearch_check.cpp"), "-o", exe, "-L", libdir, "-ldhtgpu",
-                           "-L", odir, "-loracle", "-Wl,-rpath," + libdir, "-Wl,-rpath," + odir])
-    out = subprocess.run([exe, "--run", "--quick"], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "(device paths): 0 mismatches" in out.stdout, out.stdout + out.stderr
+    import cpp_check
+    cpp_check.run(cpp_check.build("rsearch", tmp_path), ["--run", "--quick"], "rsearch_check (device paths)", 300)

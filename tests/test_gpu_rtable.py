@@ -360,14 +360,5 @@ def test_two_dev_batches_on_a_side_stream(ctx, grown):
 
 def test_cpp_adapter_resident_table(tmp_path):
     """dhtgpu::ResidentTable's device paths against its host paths and the oracle (tests/cpp/rtable_check.cpp)"""
-    import os
-    import subprocess
-    import opendht_amd
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe, libdir, odir = str(tmp_path / "rtable_check"), os.path.dirname(opendht_amd.LIB_PATH), os.path.join(root, "oracle")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "rtable_check.cpp"), "-o", exe, "-L", libdir, "-ldhtgpu",
-                           "-L", odir, "-loracle", "-Wl,-rpath," + libdir, "-Wl,-rpath," + odir])
-    out = subprocess.run([exe, "--run"], capture_output=True, text=True, timeout=120)
-    print(out.stdout)
-    assert out.returncode == 0 and "rtable_check: 0 mismatches" in out.stdout, out.stdout + out.stderr
+    import cpp_check
+    cpp_check.run(cpp_check.build("rtable", tmp_path), ["--run"], "rtable_check", 120)

@@ -488,14 +488,5 @@ def test_growth_on_a_long_lived_context(ctx):
 
 def test_cpp_adapter_follows_the_table(tmp_path):
     """dhtgpu::ResidentTable's notes and flushes against a host table, and onNewNodeBatch (tests/cpp/rtgrow_check.cpp)"""
-    import os
-    import subprocess
-    import opendht_amd
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe, libdir, odir = str(tmp_path / "rtgrow_check"), os.path.dirname(opendht_amd.LIB_PATH), os.path.join(root, "oracle")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "rtgrow_check.cpp"), "-o", exe, "-L", libdir, "-ldhtgpu",
-                           "-L", odir, "-loracle", "-Wl,-rpath," + libdir, "-Wl,-rpath," + odir])
-    out = subprocess.run([exe, "--run"], capture_output=True, text=True, timeout=120)
-    print(out.stdout)
-    assert out.returncode == 0 and "rtgrow_check: 0 mismatches" in out.stdout, out.stdout + out.stderr
+    import cpp_check
+    cpp_check.run(cpp_check.build("rtgrow", tmp_path), ["--run"], "rtgrow_check", 120)

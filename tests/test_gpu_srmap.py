@@ -3,8 +3,6 @@ opendht_amd/csrc/srmap.hip) against the model of srmap_cases.py (the walk of src
 the oracle's insertNode).  Every comparison is exact: out_cnt, out_touched, the stats (the number of
 filtered nodes included), rows, flags, lengths and status words after every step of every script, and
 the exported map.  Marked gpu: run on the MI355X box."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,7 +15,6 @@ import srmap_cases as SM
 pytestmark = pytest.mark.gpu
 
 EINVAL, ENOIDS, EUNSORTED, ERANGE = -1, -4, -5, -6
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -224,7 +221,5 @@ def test_other_families_untouched(ctx, scripts):
 def test_cpp_adapter_on_device(tmp_path):
     """tests/cpp/srmap_check.cpp --run: dhtgpu::ResidentSearches::offerBatch on mock Search / SearchNode /
     Node types, on both sides of its threshold in turn, against the oracle's walk."""
-    from test_srmap_cpu import build_srmap_check
-    exe = build_srmap_check(str(tmp_path / "srmap_check"))
-    out = subprocess.run([exe, "--run"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "(device paths): 0 mismatches" in out.stdout, out.stdout + out.stderr
+    import cpp_check
+    cpp_check.run(cpp_check.build("srmap", tmp_path), ["--run"], "srmap_check (device paths)", 120)

@@ -1,54 +1,22 @@
 """CPU-side checks of keys-to-handles over the resident NodeCache (dhtgpu_ncr_*,
-opendht_amd/csrc/ncresolve.hip): the boundary (header, exports, binding, argument errors), the model
-the GPU tests rely on checked against ncache_cases.Model, the mirrored G-switch constants, the
-kernels' register and scratch budget, and the C++ adapter's host path.  No GPU needed."""
-import ctypes
+opendht_amd/csrc/ncresolve.hip): the model the GPU tests rely on checked against ncache_cases.Model,
+the mirrored G-switch constants, and the C++ adapter's host path.  No GPU needed.  (Header, exports,
+binding and a null context: tests/test_abi.py; the kernels' register and scratch budget:
+tests/test_kernel_resources.py.)"""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_check
 import ncache_cases as NC
 import ncresolve_cases as NR
-import opendht_amd
 import oracle as O
-from test_ncache_cpu import check_unit_budget
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opendht_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-NCRS = ["dhtgpu_ncr_find", "dhtgpu_ncr_find_dev", "dhtgpu_ncr_get_nodes", "dhtgpu_ncr_extract"]
-EINVAL = -1
-
-
-def test_header_library_and_binding_agree():
-    src = open(os.path.join(ROOT, "include", "dhtgpu.h")).read()
-    declared = set(re.findall(r"^int (dhtgpu_ncr_[a-z0-9_]+)\(", src, re.M))
-    assert declared == set(NCRS)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", opendht_amd.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert {s for s in exported if s.startswith("dhtgpu_ncr_")} == set(NCRS)
-    assert {s for s in opendht_amd.exported_symbols() if s.startswith("dhtgpu_ncr_")} == set(NCRS)
-    L = opendht_amd.lib()
-    for s in NCRS:
-        assert getattr(L, s).argtypes is not None, s
-    for m in ("ncr_find", "ncr_find_dev", "ncr_get_nodes", "ncr_extract"):
-        assert callable(getattr(opendht_amd.Context, m)), m
-
-
-def test_null_context_is_einval():
-    L = opendht_amd.lib()
-    b20 = (ctypes.c_uint8 * 20)()
-    u8 = ctypes.cast(b20, ctypes.POINTER(ctypes.c_uint8))
-    w = (ctypes.c_uint32 * 16)()
-    u32 = ctypes.cast(w, ctypes.POINTER(ctypes.c_uint32))
-    assert L.dhtgpu_ncr_find(None, u8, 1, u32, None) == EINVAL
-    assert L.dhtgpu_ncr_find_dev(None, None, 0, 0, None, None, None) == EINVAL
-    assert L.dhtgpu_ncr_get_nodes(None, u8, 1, u32, 1, None, u32, None, None) == EINVAL
-    assert L.dhtgpu_ncr_extract(None, u8, 1, u32) == EINVAL
 
 
 # ---- the model against ncache_cases.Model ----------------------------------------------------------
@@ -146,35 +114,11 @@ def test_mirrored_constants_match_the_library():
     assert mfb and int(mfb.group(1)) % 64 == 0
 
 
-# mangled-name fragment -> max VGPRs.  The find holds a key, a range and one pivot; the others are
-# streaming passes: every kernel is built for 8 waves / SIMD, i.e. at most 64 VGPRs; compiled:
-VGPR_CAPS = {
-    "k_ncr_findILj64EE": 64,     # 24  one wave per key
-    "k_ncr_findILj16EE": 64,     # 24  16 lanes per key
-    "k_ncr_orderILb1EE": 64,     # 5   the blocks' counts
-    "k_ncr_orderILb0EE": 64,     # 14  the positions
-    "k_ncr_assignE": 64,         # 22
-    "k_ncr_extractE": 64,        # 6
-}
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_ncresolve_kernels_no_scratch_and_vgpr_budget():
-    check_unit_budget("ncresolve.hip", VGPR_CAPS)
-
-
 # ---- the C++11 adapter ---------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def ncresolve_check(tmp_path_factory):
     """tests/cpp/ncresolve_check.cpp built as C++11 with -Wall -Wextra -Werror"""
-    exe = str(tmp_path_factory.mktemp("ncresolve") / "ncresolve_check")
-    libdir = os.path.dirname(opendht_amd.LIB_PATH)
-    odir = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-s", "-C", odir])
-    subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "ncresolve_check.cpp"), "-o", exe, "-L", libdir, "-ldhtgpu",
-                           "-L", odir, "-loracle", "-Wl,-rpath," + libdir, "-Wl,-rpath," + odir])
-    return exe
+    return cpp_check.build("ncresolve", tmp_path_factory.mktemp("ncresolve"))
 
 
 def test_adapter_compiles_as_cxx11(ncresolve_check):
@@ -184,5 +128,4 @@ def test_adapter_compiles_as_cxx11(ncresolve_check):
 def test_adapter_host_path_and_bookkeeping(ncresolve_check):
     """slotsOfBatch below its threshold, getNodeBatch's bookkeeping against a std::map restatement of
     dhtgpu_ncr_get_nodes, free-list reuse after noteErase, an expired node made anew in its slot"""
-    out = subprocess.run([ncresolve_check, "--host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "(host paths): 0 mismatches" in out.stdout, out.stdout + out.stderr
+    cpp_check.run(ncresolve_check, ["--host"], "ncresolve_check (host paths)", 120)

@@ -1,59 +1,17 @@
 """CPU-side checks of the growing resident routing table (dhtgpu_rtg_*, opendht_amd/csrc/rtgrow.hip):
-the boundary (header, exports, binding, a NULL context), the Python model of tests/rtgrow_cases.py
-pinned to the oracle's table in the all-good regime, the model's state rules on hand-made rows, the
-kernels' register, scratch and LDS budget, and the C++ adapter's host paths.  No GPU needed."""
-import ctypes
-import os
-import re
-import shutil
+the Python model of tests/rtgrow_cases.py pinned to the oracle's table in the all-good regime, the
+model's state rules on hand-made rows, the kernels' LDS, and the C++ adapter's host paths.  No GPU
+needed.  (Header, exports, binding, the pinned constants and a null context: tests/test_abi.py; the
+kernels' register and scratch budget: tests/test_kernel_resources.py.)"""
 import subprocess
 
 import numpy as np
 import pytest
 
-import opendht_amd
+import cpp_check
+import kernel_budget as KB
 import oracle as O
 import rtgrow_cases as C
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "opendht_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-RTG = ["dhtgpu_rtg_on_new_node", "dhtgpu_rtg_expire", "dhtgpu_rtg_set_state", "dhtgpu_rtg_update_state",
-       "dhtgpu_rtg_size", "dhtgpu_rtg_export"]
-EINVAL = -1
-
-
-def test_header_library_and_binding_agree():
-    src = open(os.path.join(ROOT, "include", "dhtgpu.h")).read()
-    declared = set(re.findall(r"^int (dhtgpu_rtg_[a-z0-9_]+)\(", src, re.M))
-    assert declared == set(RTG)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", opendht_amd.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert set(RTG) <= exported
-    assert set(RTG) <= set(opendht_amd.exported_symbols())
-    L = opendht_amd.lib()
-    for s in RTG:
-        assert getattr(L, s).argtypes is not None, s
-    for m in ("rtg_on_new_node", "rtg_expire", "rtg_set_state", "rtg_update_state", "rtg_size", "rtg_export"):
-        assert callable(getattr(opendht_amd.Context, m)), m
-    for name, val in (("NONE", 0), ("KNOWN", 1), ("PLACED", 2), ("REPLACED", 3), ("FULL", 4), ("UNAPPLIED", 5)):
-        assert re.search(rf"^#define DHTGPU_RTG_{name} {val}\b", src, re.M), name
-        assert getattr(opendht_amd, "RTG_" + name) == val == getattr(C, "RTG_" + name)
-    assert re.search(r"^#define DHTGPU_RTG_MAX_HANDLE 65536u", src, re.M) and opendht_amd.RTG_MAX_HANDLE == 65536
-
-
-def test_null_context_is_einval():
-    L = opendht_amd.lib()
-    b20 = (ctypes.c_uint8 * 20)()
-    u8 = ctypes.cast(b20, ctypes.POINTER(ctypes.c_uint8))
-    w = (ctypes.c_uint32 * 16)()
-    u32 = ctypes.cast(w, ctypes.POINTER(ctypes.c_uint32))
-    assert L.dhtgpu_rtg_on_new_node(None, u8, u32, u8, None, 1, 0, u8, u32, u32) == EINVAL
-    assert L.dhtgpu_rtg_expire(None, u32, u32) == EINVAL
-    assert L.dhtgpu_rtg_set_state(None, u8, 1) == EINVAL
-    assert L.dhtgpu_rtg_update_state(None, u32, u8, 1) == EINVAL
-    assert L.dhtgpu_rtg_size(None, u32, u32) == EINVAL
-    assert L.dhtgpu_rtg_export(None, u8, u32, u8, u32, u8) == EINVAL
 
 
 # ---- the model is pinned by the oracle ------------------------------------------------------------
@@ -144,46 +102,15 @@ def test_model_stops_at_256_buckets():
 
 
 # ---- the kernels' budget --------------------------------------------------------------------------
-# mangled-name fragment -> max VGPRs, each a few registers above the figure this compile prints
-# (beside it).  The two table kernels run as one workgroup, so their cap guards against a spill, not
-# for occupancy; the three one-thread-per-entry kernels keep 8 waves / SIMD.
-VGPR_CAPS = {
-    "k_rtgILb0E": 64,          # 59  onNewNode batch
-    "k_rtgILb1E": 36,          # 31  expireBuckets
-    "k_rtg_set_stateE": 12,    # 6
-    "k_rtg_updateE": 12,       # 6
-    "k_rtg_handlesE": 10,      # 4
-}
 LDS_MAX = 160 * 1024           # one gfx950 workgroup; the table kernels hold 100,416 B
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_rtgrow_kernels_no_scratch_lds_and_vgpr_budget():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-c",
-                          os.path.join(CSRC, "rtgrow.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, cwd=CSRC, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kern, usage = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            kern = m.group(1)
-            usage[kern] = {}
-            continue
-        m = re.search(r"(VGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and kern:
-            usage[kern][m.group(1).split()[0]] = int(m.group(2))
-    assert usage, "no kernel resource remarks parsed"
-    spills = {k: v["ScratchSize"] for k, v in usage.items() if v.get("ScratchSize", 0)}
-    assert not spills, f"kernels using scratch: {spills}"
-    seen = set()
+@pytest.mark.skipif(KB.HIPCC is None, reason="hipcc not installed")
+def test_rtgrow_kernels_lds():
+    """(registers and scratch: tests/test_kernel_resources.py)"""
+    usage = KB.usage("rtgrow")
     for k, v in usage.items():
-        frags = [f for f in VGPR_CAPS if re.search(rf"\d{f}", k)]
-        assert len(frags) == 1, f"{k}: a kernel of rtgrow.hip without a cap"
-        seen.add(frags[0])
-        assert v["VGPRs"] <= VGPR_CAPS[frags[0]], f"{k}: {v['VGPRs']} VGPRs > {VGPR_CAPS[frags[0]]}"
         assert v["LDS"] <= LDS_MAX, f"{k}: {v['LDS']} B of LDS"
-    assert seen == set(VGPR_CAPS), f"kernels not found: {set(VGPR_CAPS) - seen}"
     assert max(v["LDS"] for v in usage.values()) > 64 * 1024   # the table kernels' LDS is static: the remark counts it
 
 
@@ -191,14 +118,7 @@ def test_rtgrow_kernels_no_scratch_lds_and_vgpr_budget():
 @pytest.fixture(scope="module")
 def rtgrow_check(tmp_path_factory):
     """tests/cpp/rtgrow_check.cpp built as C++11 with -Wall -Wextra -Werror against the mock table shape"""
-    exe = str(tmp_path_factory.mktemp("rtgrow") / "rtgrow_check")
-    libdir = os.path.dirname(opendht_amd.LIB_PATH)
-    odir = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-s", "-C", odir])
-    subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "rtgrow_check.cpp"), "-o", exe, "-L", libdir, "-ldhtgpu",
-                           "-L", odir, "-loracle", "-Wl,-rpath," + libdir, "-Wl,-rpath," + odir])
-    return exe
+    return cpp_check.build("rtgrow", tmp_path_factory.mktemp("rtgrow"))
 
 
 def test_adapter_compiles_as_cxx11(rtgrow_check):

@@ -1,56 +1,19 @@
 """CPU-side checks of Dht::trySearchInsert over the resident searches' map (dhtgpu_srm_*,
-opendht_amd/csrc/srmap.hip): the boundary (header, exports, binding, null context); the model the GPU
-tests rely on against an independent pure-Python walk over test_oracle.py's insertNode; the
-equivalence the kernels are built on -- the filter followed by the walk of the remaining nodes equals
-the plain sequential walk, on every case, with and without removable-not-expired nodes; what the
-cases must contain; the C++ adapter's host path; the kernels' register and scratch budget; and that
-rsearch.hip still compiles to exactly its pinned kernels.  No GPU needed."""
-import ctypes
-import os
-import re
-import shutil
+opendht_amd/csrc/srmap.hip): the model the GPU tests rely on against an independent pure-Python walk
+over test_oracle.py's insertNode; the equivalence the kernels are built on -- the filter followed by
+the walk of the remaining nodes equals the plain sequential walk, on every case, with and without
+removable-not-expired nodes; what the cases must contain; and the C++ adapter's host path.  No GPU
+needed.  (Header, exports, binding and a null context: tests/test_abi.py; the kernels' register and
+scratch budget, rsearch.hip's pinned kernel set included: tests/test_kernel_resources.py.)"""
 import subprocess
 
 import numpy as np
 import pytest
 
-import opendht_amd
+import cpp_check
 import rsearch_cases as RS
 import srmap_cases as SM
 from test_oracle import py_insert_node
-from test_rsearch_cpu import VGPR_CAPS as RSEARCH_CAPS
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "opendht_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-SRMS = ["dhtgpu_srm_set", "dhtgpu_srm_set_done", "dhtgpu_srm_offer", "dhtgpu_srm_offer_dev", "dhtgpu_srm_export"]
-EINVAL = -1
-
-
-def test_header_library_and_binding_agree():
-    src = open(os.path.join(ROOT, "include", "dhtgpu.h")).read()
-    assert set(re.findall(r"^int (dhtgpu_srm_[a-z0-9_]+)\(", src, re.M)) == set(SRMS)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", opendht_amd.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert {s for s in exported if s.startswith("dhtgpu_srm_")} == set(SRMS)
-    assert set(SRMS) <= set(opendht_amd.exported_symbols())
-    L = opendht_amd.lib()
-    for s in SRMS:
-        assert getattr(L, s).argtypes is not None, s
-        assert callable(getattr(opendht_amd.Context, s[len("dhtgpu_"):])), s
-
-
-def test_null_context_is_einval():
-    L = opendht_amd.lib()
-    w = (ctypes.c_uint32 * 64)()
-    u32 = ctypes.cast(w, ctypes.POINTER(ctypes.c_uint32))
-    b = (ctypes.c_uint8 * 64)()
-    u8 = ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8))
-    assert L.dhtgpu_srm_set(None, u32, 1) == EINVAL
-    assert L.dhtgpu_srm_set_done(None, u32, u8, 1) == EINVAL
-    assert L.dhtgpu_srm_offer(None, u32, u8, 1, u32, u32, u32) == EINVAL
-    assert L.dhtgpu_srm_offer_dev(None, None, None, 0, 0, None, None, None, None) == EINVAL
-    assert L.dhtgpu_srm_export(None, u32, u8, u32) == EINVAL
 
 
 # ---- the model ----------------------------------------------------------------------------------
@@ -173,75 +136,9 @@ def test_map_order_and_duplicates():
 
 
 # ---- the C++ adapter --------------------------------------------------------------------------------
-def build_srmap_check(exe):
-    """tests/cpp/srmap_check.cpp built as C++11 with -Wall -Wextra -Werror against mock Search types"""
-    libdir = os.path.dirname(opendht_amd.LIB_PATH)
-    odir = os.path.join(ROOT, "oracle")
-    subprocess.check_call(["make", "-s", "-C", odir])
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "srmap_check.cpp"), "-o", exe, "-L", libdir, "-ldhtgpu",
-                           "-L", odir, "-loracle", "-Wl,-rpath," + libdir, "-Wl,-rpath," + odir])
-    return exe
-
-
 def test_adapter_compiles_as_cxx11_and_host_walk(tmp_path):
     """ResidentSearches::offerBatch below its threshold, and with no device behind it: the reference's
     walk on the host map against the oracle, and the pairs it queues."""
-    exe = build_srmap_check(str(tmp_path / "srmap_check"))
+    exe = cpp_check.build("srmap", tmp_path)
     assert subprocess.check_output([exe], text=True).strip() == "built"
-    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "(host paths): 0 mismatches" in out.stdout, out.stdout + out.stderr
-
-
-# ---- the kernels' budget --------------------------------------------------------------------------
-# mangled-name fragment -> max VGPRs.  The filter and the small kernels are built for 8 waves / SIMD
-# (64 VGPRs); the walk is one workgroup of 8 waves and nothing shares its CU, capped at the same step.
-VGPR_CAPS = {
-    "k_srm_gatherE": 64,    # 13
-    "k_srm_orderE": 64,     # 4
-    "k_srm_doneE": 64,      # 5
-    "k_srm_filterE": 64,    # 19
-    "k_srm_walkE": 64,      # 31
-}
-
-
-def _resource_usage(unit):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-c",
-                          os.path.join(CSRC, unit), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, cwd=CSRC, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kern, usage = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            kern = m.group(1)
-            usage[kern] = {}
-            continue
-        m = re.search(r"(VGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and kern:
-            usage[kern][m.group(1).split()[0]] = int(m.group(2))
-    assert usage, "no kernel resource remarks parsed"
-    return usage
-
-
-def _check_caps(usage, caps, unit):
-    spills = {k: v["ScratchSize"] for k, v in usage.items() if v.get("ScratchSize", 0)}
-    assert not spills, f"kernels using scratch: {spills}"
-    seen = set()
-    for k, v in usage.items():
-        frags = [f for f in caps if re.search(rf"\d{f}", k)]
-        assert len(frags) == 1, f"{k}: a kernel of {unit} without a cap"
-        seen.add(frags[0])
-        assert v["VGPRs"] <= caps[frags[0]], f"{k}: {v['VGPRs']} VGPRs > {caps[frags[0]]}"
-    assert seen == set(caps), f"kernels not found: {set(caps) - seen}"
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_srmap_kernels_no_scratch_and_vgpr_budget():
-    _check_caps(_resource_usage("srmap.hip"), VGPR_CAPS, "srmap.hip")
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_rsearch_still_compiles_to_its_pinned_kernels():
-    """the row helpers moved to sr_row_dev.h: rsearch.hip holds exactly the kernels it held, inside their caps"""
-    _check_caps(_resource_usage("rsearch.hip"), RSEARCH_CAPS, "rsearch.hip")
+    cpp_check.run(exe, ["--host"], "srmap_check (host paths)", 120)
