@@ -41,6 +41,9 @@
  *                          one wave per search
  *   dhtgpu_sr_refill       Dht::refill (src/dht.cpp:656-677): getCachedNodes over the nc mirror + insertNode, fused
  *   dhtgpu_sr_status       Search::getNumberOfBadNodes / getNumberOfConsecutiveBadNodes (src/search.h:516-530)
+ *   dhtgpu_srs_step        Dht::searchStep (src/dht.cpp:562-654) of a find_node search over those lists: refill,
+ *                          isSynced / setDone, the next find_node targets, expiry
+ *   dhtgpu_srs_set_clock/_set_request/_entries  its clock, the request state of an entry, the entries' state
  *
  * Threading (mirrors the reference, src/dhtrunner.cpp:115-150): one context per
  * thread, or external locking; every host-pointer call is synchronous.
@@ -632,7 +635,59 @@ int dhtgpu_sr_lists(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t
 int dhtgpu_sr_lists_dev(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
                         uint32_t* out_len, void* stream);
 
-/* ---- K10m: Dht::trySearchInsert over the searches' ordered map ---------------------------------- */
+/* ---- K10s: Dht::searchStep on the resident searches -------------------------------------------- */
+/* Dht::searchStep (src/dht.cpp:562-654) for the search with no callbacks, announces or listeners --
+ * the find_node search of bootstrap, maintenance and a crawl -- on the rows of dhtgpu_sr_*, one wave
+ * per search.  The per-SearchNode state it reads travels with the entry through every insertion,
+ * trim and removal of the sr and srm families:
+ *   req    the net::Request state of getStatus[ANY_QUERY]: 0 none (erased, expired-and-over and
+ *          cancelled alike), 1 pending, 2 completed
+ *   tick   SearchNode::last_get_reply in the caller's clock ticks; 0 is time_point::min()
+ * and per slot refill_tick, Search::refill_time (0: never).  A newly inserted entry has req 0 and
+ * tick 0; dhtgpu_sr_open zeroes refill_tick.  The context holds a CLOCK, 0 until dhtgpu_srs_set_clock
+ * (scheduler.time(); now == 0 is DHTGPU_ERANGE; no device work): from then on an insertion that
+ * carries a token also sets the entry's tick to the clock (src/search.h:712-718) and every refill
+ * sets refill_tick to it (src/dht.cpp:658).
+ *
+ * dhtgpu_srs_set_request: req = val[j] in {0, 1, 2} (else DHTGPU_EINVAL before any launch) for m
+ * (slot, handle) pairs, with dhtgpu_sr_set_candidate's rules: an absent handle changes nothing,
+ * stream-ordered, no synchronise.  2 is what the engine does before searchNodeGetDone, 0 is
+ * searchNodeGetExpired's erase when over (src/dht.cpp:251-252).
+ *
+ * dhtgpu_srs_step, per listed search, with now = the clock and E = node_expire (ticks; sums in 64 bits):
+ *   1. expired or done on entry: nothing changes, bit `skipped`
+ *   2. refill_count != 0 && refill_tick + E < now && len - bad nodes < SEARCH_NODES: Dht::refill as
+ *      dhtgpu_sr_refill(count = refill_count) runs it, then refill_tick = now
+ *   3. Search::isSynced(now) (src/search.h:734-747) -- each of the first TARGET_NODES = 8 non-bad entries
+ *      has replied and tick != 0 && tick + E >= now, and there is one -- then setDone(): done = 1, every
+ *      req = 0, nothing is sent
+ *   4. otherwise, while fewer than MAX_REQUESTED_SEARCH_NODES = 4 non-bad entries are pending, the
+ *      first entry in list order with canGet (src/search.h:139-161 for the one query: the node not
+ *      expired and req == 0, or req == 2 and (tick == 0 or now > tick + E)) gets req = 1 and its handle is
+ *      appended to out_send[j]; a candidate entry is sent to and not counted
+ *   5. leading bad nodes >= min(len, SEARCH_MAX_BAD_NODES = 25): Search::expire() (src/search.h:560-567) --
+ *      expired = 1, the list cleared, done = 1.  (dhtgpu_sr_expire itself leaves done alone.)
+ * out_send[m * DHTGPU_SR_CAP] rows are DHTGPU_NONE padded; out4[j*4 ..] = {sends, pending non-bad
+ * entries after, nodes the refill inserted, bits: bit0 expired after, bit1 overflowed, bit2 done after,
+ * bit3 refilled, bit4 synced, bit5 skipped}.  DHTGPU_EINVAL before the first dhtgpu_srs_set_clock.
+ * refill_count 0 skips step 2 and needs no nc mirror; 1..DHTGPU_MAX_K needs one, else DHTGPU_ENOIDS.
+ * Host form: the slots are distinct (DHTGPU_EINVAL otherwise); on a row overflow DHTGPU_ERANGE after
+ * applying everything, as dhtgpu_sr_refill.  _dev: device arrays, a stream (NULL = the context's), a
+ * slot >= nslots is skipped (its output rows are not written); neither synchronises nor allocates.
+ *
+ * dhtgpu_srs_entries: out_req / out_tick [m * DHTGPU_SR_CAP] (either nullable), 0 past a row's end. */
+int dhtgpu_srs_set_clock(dhtgpu_ctx* ctx, uint32_t now);
+int dhtgpu_srs_set_request(dhtgpu_ctx* ctx, const uint32_t* slots, const uint32_t* handles, const uint8_t* val,
+                           uint32_t m);
+int dhtgpu_srs_step(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t node_expire, uint32_t refill_count,
+                    uint32_t* out_send, uint32_t* out4);
+int dhtgpu_srs_step_dev(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint32_t node_expire,
+                        uint32_t refill_count, uint32_t* out_send, uint32_t* out4, void* stream);
+int dhtgpu_srs_entries(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint8_t* out_req, uint32_t* out_tick);
+int dhtgpu_srs_entries_dev(dhtgpu_ctx* ctx, const uint32_t* slots, uint32_t m, uint8_t* out_req, uint32_t* out_tick,
+                           void* stream);
+
+/* ---- K10m:Dht::trySearchInsert over the searches' ordered map ---------------------------------- */
 /* Dht::trySearchInsert (src/dht.cpp:118-150) for a batch of learned nodes over the resident searches
  * of dhtgpu_sr_*: the reference's searches(af) -- a std::map by target -- is the MAP, a set of slots
  * the library keeps in ascending order of their targets.  For node j of a batch, each taken strictly

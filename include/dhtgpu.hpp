@@ -1075,7 +1075,10 @@ private:
  *                               (closed slots go on a free list, like the cache's)
  *   noteInsert(slot, node, has_token)   where the reply path calls sr->insertNode(node, now, token)
  *   noteCandidate(slot, node, val)      where Dht::searchNodeGetExpired sets srn->candidate
- *                               -- all three only queue: no device call before the next flush
+ *   noteRequest(slot, node, state)      where a find_node request completes or is erased (see the method)
+ *                               -- all four only queue: no device call before the next flush
+ *   stepBatch(slots, q, now_tick, node_expire)   Dht::searchStep for q find_node searches on the
+ *                               device; returns the nodes to send find_node to (see the method)
  *   refresh(now)                once per sweep: flushes the queue, then isExpired() | isRemovable(now) << 1
  *                               of every live cache slot, as one upload
  *   refillBatch(searches, slots, q, now)   Dht::refill for q searches; returns the inserted counts
@@ -1142,7 +1145,7 @@ public:
     void close(uint32_t slot) {
         size_t w = 0;
         for (size_t i = 0; i < log_.size(); ++i)
-            if (log_[i].slot != slot) log_[w++] = log_[i];
+            if (log_[i].kind == kClock || log_[i].slot != slot) log_[w++] = log_[i];
         log_.resize(w);
         free_.push_back(slot);
         const auto t = target_of_slot_.find(slot);
@@ -1161,6 +1164,18 @@ public:
         Op op = {kCandidate, slot, (uint8_t)(val ? 1 : 0), Key(), node};
         log_.push_back(op);
     }
+    /* the request state of the node's entry (0 none, 1 pending, 2 completed): 2 where the engine
+     * completes the request before Dht::searchNodeGetDone, 0 where searchNodeGetExpired erases it */
+    void noteRequest(uint32_t slot, const NodePtr& node, unsigned state) {
+        Op op = {kRequest, slot, (uint8_t)state, Key(), node};
+        log_.push_back(op);
+    }
+    /* scheduler.time() in ticks (> 0) from here on in the queue: the last_get_reply of the replies
+     * queued after it.  stepBatch queues its own. */
+    void noteClock(uint32_t now_tick) {
+        Op op = {kClock, now_tick, 0, Key(), NodePtr()};
+        log_.push_back(op);
+    }
     size_t pending() const { return log_.size(); }
     size_t freeSlots() const { return free_.size(); }
 
@@ -1173,7 +1188,8 @@ public:
             while (e < log_.size() && log_[e].kind == log_[i].kind) ++e;
             if (log_[i].kind == kOpen) flush_open(i, e);
             else if (log_[i].kind == kInsert) flush_insert(i, e);
-            else flush_candidate(i, e);
+            else if (log_[i].kind == kClock) check(dhtgpu_srs_set_clock(ctx(), log_[e - 1].slot), "srs_set_clock");
+            else flush_pairs(i, e, log_[i].kind == kRequest);
             i = e;
         }
         log_.clear();
@@ -1250,12 +1266,50 @@ public:
         return res;
     }
 
+    /* What Dht::searchStep decided for one search: the nodes to send find_node to, in list order, and
+     * dhtgpu_srs_step's out4 -- pending non-bad entries after, nodes the refill inserted, bits. */
+    struct Step {
+        std::vector<NodePtr> send;
+        uint32_t solicited, inserted, bits;
+        bool expired() const { return (bits & 1u) != 0; }
+        bool done() const { return (bits & 4u) != 0; }
+        bool synced() const { return (bits & 16u) != 0; }
+        bool skipped() const { return (bits & 32u) != 0; }
+    };
+    /* Dht::searchStep (src/dht.cpp:562-654) for q find_node searches whose request state lives with
+     * the device (noteRequest): flushes the queues, sets the clock to now_tick (> 0), runs
+     * dhtgpu_srs_step and returns its decisions.  The caller sends find_node to every node of
+     * Step::send -- the device already holds those requests as pending -- and reports each outcome
+     * with noteRequest / noteInsert / noteCandidate.  No host Search is read or written. */
+    std::vector<Step> stepBatch(const uint32_t* slots, size_t q, uint32_t now_tick, uint32_t node_expire,
+                                uint32_t refill_count = 14) {
+        std::vector<Step> res(q);
+        if (q == 0) return res;
+        cache_.flush();
+        noteClock(now_tick);
+        flush();
+        std::vector<uint32_t> send(q * DHTGPU_SR_CAP), out4(q * 4);
+        const int rc = dhtgpu_srs_step(ctx(), slots, (uint32_t)q, node_expire, refill_count, send.data(), out4.data());
+        if (rc != DHTGPU_ERANGE) check(rc, "srs_step");   // an overflowed row is still a valid list
+        const auto& sl = cache_.slots().slots_;
+        for (size_t i = 0; i < q; ++i) {
+            for (uint32_t k = 0; k < out4[i * 4]; ++k) {
+                const uint32_t h = send[i * DHTGPU_SR_CAP + k];
+                if (NodePtr n = h < sl.size() ? sl[h].lock() : NodePtr()) res[i].send.push_back(n);
+            }
+            res[i].solicited = out4[i * 4 + 1];
+            res[i].inserted = out4[i * 4 + 2];
+            res[i].bits = out4[i * 4 + 3];
+        }
+        return res;
+    }
+
 private:
-    enum Kind { kOpen, kInsert, kCandidate };
+    enum Kind { kOpen, kInsert, kCandidate, kRequest, kClock };
     struct Op {
         Kind kind;
-        uint32_t slot;
-        uint8_t val;    // insert: replied with a token; candidate: the flag
+        uint32_t slot;  // clock: the tick
+        uint8_t val;    // insert: replied with a token; candidate: the flag; request: the state
         Key key;        // open: the target
         NodePtr node;   // insert, candidate: the node (its cache slot is looked up when the queue is flushed,
     };                  //   so queueing costs no key lookup; a node the cache dropped meanwhile is skipped)
@@ -1331,7 +1385,7 @@ private:
                                         tok.data(), nullptr);
         if (rc != DHTGPU_ERANGE) check(rc, "sr_insert");
     }
-    void flush_candidate(size_t b, size_t e) {   // of equal (slot, handle) pairs the last one counts
+    void flush_pairs(size_t b, size_t e, bool request) {   // candidate flags or request states: of equal (slot, handle) pairs the last one counts
         std::map<std::pair<uint32_t, uint32_t>, uint8_t> last;
         for (size_t i = b; i < e; ++i) {
             const uint32_t h = cache_.slots().slotOf(log_[i].node->id);
@@ -1345,8 +1399,12 @@ private:
             handles.push_back(kv.first.second);
             val.push_back(kv.second);
         }
-        check(dhtgpu_sr_set_candidate(ctx(), slots.data(), handles.data(), val.data(), (uint32_t)slots.size()),
-              "sr_set_candidate");
+        if (request)
+            check(dhtgpu_srs_set_request(ctx(), slots.data(), handles.data(), val.data(), (uint32_t)slots.size()),
+                  "srs_set_request");
+        else
+            check(dhtgpu_sr_set_candidate(ctx(), slots.data(), handles.data(), val.data(), (uint32_t)slots.size()),
+                  "sr_set_candidate");
     }
     /* the slot of the search opened for this target (DHTGPU_NONE: none) */
     template <class HashT>

@@ -18,6 +18,7 @@ Reference interfaces mirrored (OpenDHT tree paths):
                           incrementally; getCachedNodes one wave per target (src/node_cache.cpp:42-123)
   Context.ncr_find / ncr_get_nodes / ncr_extract  NodeMap::getNode in batches over it: ids to handles
   Context.sr_reset / sr_open / sr_insert / sr_refill / sr_status / sr_lists  the searches' node lists
+  Context.srs_set_clock / srs_set_request / srs_step / srs_entries  Dht::searchStep on those lists
   Context.srm_set / srm_set_done / srm_offer / srm_export  Dht::trySearchInsert over their ordered map
                           resident on the device: Search::insertNode one wave per search
                           (src/search.h:636-722), Dht::refill fused with getCachedNodes (src/dht.cpp:656-677)
@@ -187,6 +188,12 @@ _SIG = {
         "dhtgpu_sr_status_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
         "dhtgpu_sr_lists": ([_vp, _u32p, ctypes.c_uint32, _u32p, _u8p, _u32p], ctypes.c_int),
         "dhtgpu_sr_lists_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "dhtgpu_srs_set_clock": ([_vp, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_srs_set_request": ([_vp, _u32p, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
+        "dhtgpu_srs_step": ([_vp, _u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p], ctypes.c_int),
+        "dhtgpu_srs_step_dev": ([_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp], ctypes.c_int),
+        "dhtgpu_srs_entries": ([_vp, _u32p, ctypes.c_uint32, _u8p, _u32p], ctypes.c_int),
+        "dhtgpu_srs_entries_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp], ctypes.c_int),
         "dhtgpu_srm_set": ([_vp, _u32p, ctypes.c_uint32], ctypes.c_int),
         "dhtgpu_srm_set_done": ([_vp, _u32p, _u8p, ctypes.c_uint32], ctypes.c_int),
         "dhtgpu_srm_offer": ([_vp, _u32p, _u8p, ctypes.c_uint32, _u32p, _u32p, _u32p], ctypes.c_int),
@@ -834,6 +841,52 @@ class Context:
     def sr_lists_dev(self, slots_ptr, m, out_handle_ptr, out_flags_ptr=None, out_len_ptr=None, stream=None):
         _check(lib().dhtgpu_sr_lists_dev(self._h, slots_ptr, m, out_handle_ptr, out_flags_ptr, out_len_ptr, stream),
                "sr_lists_dev")
+
+    # ---- K10s: Dht::searchStep on the resident searches -----------------------------------
+    def srs_set_clock(self, now):
+        """scheduler.time() in the caller's ticks (> 0): what token insertions, refills and steps read."""
+        _check(lib().dhtgpu_srs_set_clock(self._h, int(now)), "srs_set_clock")
+
+    def srs_set_request(self, slots, handles, val):
+        """req (0 none, 1 pending, 2 completed) of handles[j]'s entry in slots[j] = val[j]; an absent
+        handle changes nothing."""
+        s, h = self._u32(slots), self._u32(handles)
+        if s.shape[0] != h.shape[0]:
+            raise ValueError("one handle per slot")
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(val), h.shape)).astype(np.uint8).reshape(-1)
+        _check(lib().dhtgpu_srs_set_request(self._h, _p(s, _u32p), _p(h, _u32p), _p(v, _u8p), s.shape[0]),
+               "srs_set_request")
+
+    def srs_step(self, slots, node_expire, refill_count=14):
+        """Dht::searchStep per slot: ((m, 64) handles to send find_node to, NONE padded; (m, 4) uint32
+        sends, pending non-bad entries after, refill's inserted count, bits).  Raises ERANGE (after
+        applying everything) when a refill overflowed a row -- the results in the exception's `result`."""
+        s = self._u32(slots)
+        m = s.shape[0]
+        send = np.full((m, SR_CAP), NONE, dtype=np.uint32)
+        out4 = np.zeros((m, 4), dtype=np.uint32)
+        code = lib().dhtgpu_srs_step(self._h, _p(s, _u32p), m, node_expire, refill_count, _p(send, _u32p), _p(out4, _u32p))
+        if code != 0:
+            e = DhtGpuError(code, "srs_step")
+            e.result = (send, out4)
+            raise e
+        return send, out4
+
+    def srs_entries(self, slots):
+        """The rows' request state and ticks: (m, 64) uint8 req, (m, 64) uint32 tick, 0 past a row's end."""
+        s = self._u32(slots)
+        m = s.shape[0]
+        req = np.zeros((m, SR_CAP), dtype=np.uint8)
+        tick = np.zeros((m, SR_CAP), dtype=np.uint32)
+        _check(lib().dhtgpu_srs_entries(self._h, _p(s, _u32p), m, _p(req, _u8p), _p(tick, _u32p)), "srs_entries")
+        return req, tick
+
+    def srs_step_dev(self, slots_ptr, m, node_expire, refill_count, out_send_ptr, out4_ptr, stream=None):
+        _check(lib().dhtgpu_srs_step_dev(self._h, slots_ptr, m, node_expire, refill_count, out_send_ptr, out4_ptr, stream),
+               "srs_step_dev")
+
+    def srs_entries_dev(self, slots_ptr, m, out_req_ptr, out_tick_ptr, stream=None):
+        _check(lib().dhtgpu_srs_entries_dev(self._h, slots_ptr, m, out_req_ptr, out_tick_ptr, stream), "srs_entries_dev")
 
     # ---- K10m: Dht::trySearchInsert over the searches' ordered map -----------------------
     def srm_set(self, slots):

@@ -293,6 +293,8 @@ struct dhtgpu_ctx {
     // entry points, staging included; refill reads the nc mirror through nc.view().
     struct Searches {
         DevBuf rows, tp, len, bits;
+        DevBuf tick, rtick;         // the entries' last_get_reply plane; refill_time per slot
+        uint32_t clock = 0;         // dhtgpu_srs_set_clock: passed by value to every launch, 0 until set
         uint32_t nslots = 0;
         DevBuf st, st_old;
         uint32_t nst = 0;           // the state array's extent
@@ -300,7 +302,8 @@ struct dhtgpu_ctx {
         bool valid = false;
         SrView view() const {
             return SrView{nslots, rows.as<uint32_t>(), (uint64_t)nslots * DHTGPU_SR_CAP, tp.as<uint32_t>(),
-                          len.as<uint32_t>(), bits.as<uint8_t>(), st.as<uint8_t>(), nst};
+                          len.as<uint32_t>(), bits.as<uint8_t>(), st.as<uint8_t>(), nst,
+                          tick.as<uint32_t>(), rtick.as<uint32_t>(), clock};
         }
         // K10m (dhtgpu_srm_*): the searches' ordered map -- the mapped slots in target order and the
         // sorted target planes -- and an offer's work arrays, all sized by dhtgpu_srm_set so that an

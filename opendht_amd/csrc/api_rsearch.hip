@@ -1,6 +1,6 @@
 // api_rsearch.hip -- the C ABI's resident searches: K10w (dhtgpu_sr_*: the searches' node lists,
-// insertNode and the fused refill) and K10m (dhtgpu_srm_*: trySearchInsert over their ordered
-// map).  The one unit that touches the context's sr state; of nc it reads valid and view() only.
+// insertNode and the fused refill), K10s (dhtgpu_srs_*: searchStep on those lists) and K10m
+// (dhtgpu_srm_*: trySearchInsert over their ordered map).  The one unit that touches the context's sr state; of nc it reads valid and view() only.
 #include "api_ctx.h"
 
 // every slot names a search; `distinct`: no slot twice
@@ -62,6 +62,21 @@ static int srm_offer_on(dhtgpu_ctx* c, const uint32_t* handles, const uint32_t* 
     return DHTGPU_OK;
 }
 
+// the argument checks of both forms of dhtgpu_srs_step
+static int srs_step_check(const dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t refill_count,
+                          const uint32_t* out_send, const uint32_t* out4) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (refill_count > DHTGPU_MAX_K || (m && (!out_send || !out4))) return DHTGPU_EINVAL;
+    if (c->sr.clock == 0) return DHTGPU_EINVAL;   // no dhtgpu_srs_set_clock yet
+    if (refill_count && !c->nc.valid) return DHTGPU_ENOIDS;
+    return DHTGPU_OK;
+}
+
+// the NodeCache mirror a step's refill leg walks; without one (refill_count 0) it is never read
+static NcView srs_nc(const dhtgpu_ctx* c, uint32_t refill_count) {
+    return refill_count ? c->nc.view() : NcView{0, nullptr, 0, nullptr, nullptr};
+}
+
 extern "C" {
 
 // ---- K10w: the resident searches ---------------------------------------------------------------
@@ -82,6 +97,10 @@ int dhtgpu_sr_reset(dhtgpu_ctx* c, uint32_t nslots) {
     DHT_TRY(t.tp.ensure(ns * 5 * 4));
     DHT_TRY(t.len.ensure(ns * 4));
     DHT_TRY(t.bits.ensure(ns));
+    DHT_TRY(t.tick.ensure(ns * DHTGPU_SR_CAP * 4));
+    DHT_TRY(t.rtick.ensure(ns * 4));
+    DHT_TRY(hipMemsetAsync(t.tick.p, 0, ns * DHTGPU_SR_CAP * 4, c->stream));
+    DHT_TRY(hipMemsetAsync(t.rtick.p, 0, ns * 4, c->stream));
     DHT_TRY(hipMemsetAsync(t.tp.p, 0, ns * 5 * 4, c->stream));
     DHT_TRY(hipMemsetAsync(t.len.p, 0, ns * 4, c->stream));
     DHT_TRY(hipMemsetAsync(t.bits.p, 0, ns, c->stream));
@@ -286,6 +305,91 @@ int dhtgpu_sr_lists(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t* 
     DHT_TRY(hipMemcpyAsync(out_handle, p[1], sz[1], hipMemcpyDeviceToHost, c->stream));
     if (out_flags) DHT_TRY(hipMemcpyAsync(out_flags, p[2], sz[2], hipMemcpyDeviceToHost, c->stream));
     if (out_len) DHT_TRY(hipMemcpyAsync(out_len, p[3], sz[3], hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipStreamSynchronize(c->stream));
+    return DHTGPU_OK;
+}
+
+// ---- K10s: Dht::searchStep for find_node searches ------------------------------------------------
+int dhtgpu_srs_set_clock(dhtgpu_ctx* c, uint32_t now) {
+    if (!c) return DHTGPU_EINVAL;
+    if (now == 0) return DHTGPU_ERANGE;   // 0 is "never set"
+    c->sr.clock = now;
+    return DHTGPU_OK;
+}
+
+int dhtgpu_srs_set_request(dhtgpu_ctx* c, const uint32_t* slots, const uint32_t* handles, const uint8_t* val,
+                           uint32_t m) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (m && (!handles || !val)) return DHTGPU_EINVAL;
+    for (uint32_t j = 0; j < m; ++j)
+        if (val[j] > 2) return DHTGPU_EINVAL;
+    if (int r = sr_check_slots(c, slots, m, false)) return r;
+    if (!handle_extent(handles, m)) return DHTGPU_EINVAL;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const size_t sz[] = {(size_t)m * 4, (size_t)m * 4, (size_t)m};
+    uint8_t* p[3];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    if (int r = sr_upload_slots(c, p[0], slots, m)) return r;
+    DHT_TRY(hipMemcpyAsync(p[1], handles, sz[1], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(hipMemcpyAsync(p[2], val, sz[2], hipMemcpyHostToDevice, c->stream));
+    DHT_TRY(launch_srs_request(c->sr.view(), reinterpret_cast<uint32_t*>(p[0]), reinterpret_cast<uint32_t*>(p[1]), p[2], m,
+                               c->stream));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_srs_step_dev(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t node_expire, uint32_t refill_count,
+                        uint32_t* out_send, uint32_t* out4, void* stream) {
+    if (int r = srs_step_check(c, slots, m, refill_count, out_send, out4)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_srs_step(c->sr.view(), srs_nc(c, refill_count), slots, m, node_expire, refill_count, out_send, out4,
+                            nullptr, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_srs_step(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint32_t node_expire, uint32_t refill_count,
+                    uint32_t* out_send, uint32_t* out4) {
+    if (int r = srs_step_check(c, slots, m, refill_count, out_send, out4)) return r;
+    if (int r = sr_check_slots(c, slots, m, true)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    // slots | send rows | out4 | overflow word
+    const size_t sz[] = {(size_t)m * 4, (size_t)m * DHTGPU_SR_CAP * 4, (size_t)m * 16, 4};
+    uint8_t* p[4];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    if (int r = sr_upload_slots(c, p[0], slots, m)) return r;
+    DHT_TRY(hipMemsetAsync(p[3], 0, 4, c->stream));
+    DHT_TRY(launch_srs_step(c->sr.view(), srs_nc(c, refill_count), reinterpret_cast<uint32_t*>(p[0]), m, node_expire,
+                            refill_count, reinterpret_cast<uint32_t*>(p[1]), reinterpret_cast<uint32_t*>(p[2]),
+                            reinterpret_cast<uint32_t*>(p[3]), c->stream));
+    DHT_TRY(hipMemcpyAsync(out_send, p[1], sz[1], hipMemcpyDeviceToHost, c->stream));
+    DHT_TRY(hipMemcpyAsync(out4, p[2], sz[2], hipMemcpyDeviceToHost, c->stream));
+    return sr_finish(c, reinterpret_cast<uint32_t*>(p[3]));
+}
+
+int dhtgpu_srs_entries_dev(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint8_t* out_req, uint32_t* out_tick,
+                           void* stream) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    DHT_TRY(launch_srs_entries(c->sr.view(), slots, m, out_req, out_tick, c->stream_or(stream)));
+    return DHTGPU_OK;
+}
+
+int dhtgpu_srs_entries(dhtgpu_ctx* c, const uint32_t* slots, uint32_t m, uint8_t* out_req, uint32_t* out_tick) {
+    if (int r = sr_check(c, slots, m)) return r;
+    if (int r = sr_check_slots(c, slots, m, false)) return r;
+    if (!m) return DHTGPU_OK;
+    DHT_TRY(c->bind());
+    const size_t sz[] = {(size_t)m * 4, (size_t)m * DHTGPU_SR_CAP, (size_t)m * DHTGPU_SR_CAP * 4};
+    uint8_t* p[3];
+    DHT_TRY(carve(c->sr.io, sz, p));
+    if (int r = sr_upload_slots(c, p[0], slots, m)) return r;
+    DHT_TRY(launch_srs_entries(c->sr.view(), reinterpret_cast<uint32_t*>(p[0]), m, p[1], reinterpret_cast<uint32_t*>(p[2]),
+                               c->stream));
+    if (out_req) DHT_TRY(hipMemcpyAsync(out_req, p[1], sz[1], hipMemcpyDeviceToHost, c->stream));
+    if (out_tick) DHT_TRY(hipMemcpyAsync(out_tick, p[2], sz[2], hipMemcpyDeviceToHost, c->stream));
     DHT_TRY(hipStreamSynchronize(c->stream));
     return DHTGPU_OK;
 }

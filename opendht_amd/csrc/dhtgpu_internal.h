@@ -376,12 +376,15 @@ hipError_t launch_ncr_extract(const NcView& v, const uint32_t* perm, const uint3
 struct SrView {
     uint32_t nslots;
     uint32_t* ep;            // six entry planes, ep[w * es + slot * 64 + l]: the five words of entry l's
-    uint64_t es;             //   distance to the slot's target, then its handle | flags << 28; es = nslots * 64
+    uint64_t es;             //   distance to the slot's target, then its handle | flags << 28 | req << 30; es = nslots * 64
     uint32_t* tp;            // target word planes, tp[w * nslots + slot]
     uint32_t* len;           // [nslots] list lengths (<= 64)
     uint8_t* bits;           // [nslots] bit0 Search::expired, bit1 overflowed, bit2 Search::done
     const uint8_t* st;       // node state by handle (bit0 isExpired(), bit1 isRemovable(now)), [nst]
     uint32_t nst;            //   a handle at or past nst reads as 0
+    uint32_t* tk;            // the entries' tick plane, tk[slot * 64 + l]: SearchNode::last_get_reply, 0 = min()
+    uint32_t* rtick;         // [nslots] Search::refill_time in clock ticks, 0 = never
+    uint32_t clock;          // the context's clock (dhtgpu_srs_set_clock), 0 until set
 };
 // Search::insertNode + removeExpiredNode: slot slots[j] takes insertions [ins_off[j], ins_off[j + 1])
 // in order -- handles, id planes ip / is, token bytes (nullable: none) -- added[] (nullable) =
@@ -401,6 +404,21 @@ hipError_t launch_sr_candidate(const SrView& v, const uint32_t* slots, const uin
 hipError_t launch_sr_status(const SrView& v, const uint32_t* slots, uint32_t m, uint32_t* out4, hipStream_t s);
 hipError_t launch_sr_lists(const SrView& v, const uint32_t* slots, uint32_t m, uint32_t* out_handle, uint8_t* out_flags,
                            uint32_t* out_len, hipStream_t s);
+
+// srstep.hip: K10s, Dht::searchStep for find_node searches over the resident rows (dhtgpu_srs_*).
+// One wave per listed slot (a slot >= nslots is skipped): out_send[j * 64 + i] = the handle of the
+// i-th node to send find_node to (DHT_NONE padded), out4[j] = {sends, solicited nodes after, nodes
+// the refill inserted, bits}; node_expire in clock ticks; refill_count 0: no refill leg, nc unread.
+// *over_any (nullable) |= 1 when a refill overflowed a row.
+hipError_t launch_srs_step(const SrView& v, const NcView& nc, const uint32_t* slots, uint32_t m, uint32_t node_expire,
+                           uint32_t refill_count, uint32_t* out_send, uint32_t* out4, uint32_t* over_any,
+                           hipStream_t s);
+// req = val[j] (0, 1, 2) for the entry of handles[j] in slot slots[j] (one wave per pair; absent: nothing)
+hipError_t launch_srs_request(const SrView& v, const uint32_t* slots, const uint32_t* handles, const uint8_t* val,
+                              uint32_t m, hipStream_t s);
+// the rows' req and tick (64 per slot, 0 padded)
+hipError_t launch_srs_entries(const SrView& v, const uint32_t* slots, uint32_t m, uint8_t* out_req, uint32_t* out_tick,
+                              hipStream_t s);
 
 // srmap.hip: K10m, Dht::trySearchInsert over the searches' ordered map (dhtgpu_srm_*).  The map as
 // the kernels read it: the mapped slots in ascending order of their targets and those targets.

@@ -10,7 +10,8 @@
 // A search lives in a slot.  Its node list is a row of 64 entries in six u32 planes -- the five
 // words of the node's DISTANCE to the search's target (id ^ target), so that an ordering test is a
 // plain five-word compare and needs no target, and the node's handle with the entry's flags in bits
-// 28-29 (bit0 candidate, bit1 replied; handles are below 2^28) -- plus the target, the length and a
+// 28-29 (bit0 candidate, bit1 replied; handles are below 2^28) and srstep.hip's request state in bits
+// 30-31, and a seventh plane of ticks (SearchNode::last_get_reply) -- plus the target, the length and a
 // bits byte (bit0 Search::expired, bit1 overflowed, bit2 Search::done -- srmap.hip's) per slot.  Node state (bit0 isExpired(), bit1
 // isRemovable(now)) is a byte array by handle; a handle at or past its extent reads as 0.
 //
@@ -29,7 +30,7 @@
 // No LDS array and no global access inside the per-insertion loop.  Everything is defined by the
 // ballots, so the result equals the reference's sequential walk whether or not a row is sorted.
 // Bytes per insertion: 20 (id) + 4 (handle) + 1 (token) + 1 (state gather) read, 1 (added) written;
-// per search and call: 20 (target) + 8, and (24 + 1) x len read and 24 x len written for the row.
+// per search and call: 20 (target) + 8, and (28 + 1) x len read and 28 x len written for the row.
 // Bytes per refill: the same per search, plus k_nc's lookup (20 x 64 per search round, (24 + 4 + 1)
 // x 64 per window loaded, two at least) -- no per-insertion traffic at all.
 #include "dhtgpu_dev.h"
@@ -39,17 +40,6 @@
 
 namespace dhtgpu {
 namespace {
-
-constexpr uint32_t kSrWaves = 4;         // searches per 256-thread workgroup
-
-// wave j of the call -> its slot (wave-uniform); false: past the list or not a slot
-__device__ __forceinline__ bool sr_slot(const SrView& v, const uint32_t* __restrict__ slots, uint32_t m, uint32_t* j,
-                                        uint32_t* slot) {
-    *j = __builtin_amdgcn_readfirstlane(blockIdx.x * kSrWaves + (threadIdx.x >> 6));
-    if (*j >= m) return false;
-    *slot = __builtin_amdgcn_readfirstlane(slots[*j]);
-    return *slot < v.nslots;
-}
 
 __device__ __forceinline__ uint64_t uniform64(uint64_t x) {
     return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32) |
@@ -89,7 +79,7 @@ __global__ __launch_bounds__(256) void k_sr_insert(SrView v, const uint32_t* __r
 #pragma unroll
             for (int w = 0; w < DHT_W; ++w) xd[w] = nc_lane(cd[w], k);
             const uint32_t xs = nc_lane(cs, k);
-            const bool a = sr_insert(r, lane, xd, nc_lane(ch, k), xs & 0xFFu, (xs & 0x100u) != 0);
+            const bool a = sr_insert(r, lane, xd, nc_lane(ch, k), xs & 0xFFu, (xs & 0x100u) != 0, v.clock);
             if (lane == k) mine = a;
         }
         if (added && lane < cn) added[c0 + lane] = mine ? 1 : 0;
@@ -111,10 +101,11 @@ __global__ __launch_bounds__(256) void k_sr_refill(SrView v, NcView nc, const ui
     sr_load(v, slot, lane, r);
     uint32_t inserted = 0;
     nc_walk<true>(nc, v.st, v.nst, t, count, lane, [&](uint32_t, const uint32_t* xd, uint32_t h, uint32_t s) {
-        inserted += sr_insert(r, lane, xd, h & kHandleMask, s, false) ? 1u : 0u;
+        inserted += sr_insert(r, lane, xd, h & kHandleMask, s, false, 0u) ? 1u : 0u;
     });
     sr_store(v, slot, lane, r);
     if (lane == 0) {
+        v.rtick[slot] = v.clock;   // Search::refill_time = now
         out_inserted[j] = inserted;
         if (over_any && r.drop) atomicOr(over_any, 1u);
     }
@@ -131,6 +122,7 @@ __global__ __launch_bounds__(256) void k_sr_open(SrView v, const uint32_t* __res
     for (int w = 0; w < DHT_W; ++w) v.tp[(uint64_t)w * v.nslots + slot] = tp[(uint64_t)w * ts + j];
     v.len[slot] = 0;
     v.bits[slot] = 0;
+    v.rtick[slot] = 0;
 }
 
 // Search::expire (src/search.h:560-565): expired = true, the list cleared

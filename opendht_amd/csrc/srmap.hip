@@ -177,7 +177,7 @@ __global__ __launch_bounds__(kWalkThreads) void k_srm_walk(SrView v, SrmView mp,
 #pragma unroll
                     for (int w = 0; w < DHT_W; ++w) xd[w] = xi[w] ^ v.tp[(uint64_t)w * v.nslots + slot];
                     sr_load(v, slot, lane, r);
-                    const bool added = sr_insert(r, lane, xd, xh, xs, false);
+                    const bool added = sr_insert(r, lane, xd, xh, xs, false, 0u);
                     code = 1u | (added ? 2u : 0u) | (added || r.expired || r.done ? 4u : 0u);
                 }
             }
